@@ -7,11 +7,17 @@ rank per GPU).  One STEP = one pass of the hot path over one synthetic video: th
 propagated frames pays key encoder + memory read + decoder + aggregate, every 5th a value encode; mask
 H2D, final argmax and mask D2H are inside the timed region; clip decode/H2D and engine construction are
 not (inputs resident in HBM).  Videos shard across ranks with no data-path collective (weak scaling:
-every rank runs K videos); the only collectives are the timing barrier/max and one gather of per-video
+every rank runs K videos); the only collectives are the timing barrier/max and (``--full``) one gather of per-video
 J&F rows (RCCL over xGMI).
 
-Output: ONE JSON line on rank 0 (see the task contract; `value_repeats` = the timed region run three times, `frame_kernel_ms` /
-`kernel_ms_per_frame_by_class` = the solo leg's kernel time, `host_*` = what the lanes cost the host) with two extra objects:
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs (``--dump-outputs DIR``:
+the masks of the last video each pooled engine ran in the timed region, DIR/<name>.npy in float32, a fixed seeded sample where
+an output is large) and print ONE short JSON line on rank 0 (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` = wall time of the timed region / K, `host_*` = what the lanes cost the host).  Everything below is measured
+only with ``--full``.
+
+``--full``: the same line (`value_repeats` = the timed region run three times, `frame_kernel_ms` /
+`kernel_ms_per_frame_by_class` = the solo leg's kernel time) with two extra objects:
   roofline     - dominant kernel (fp32 implicit-GEMM conv): algorithmic FLOP of all conv launches in the
                  timed region / their summed device time (HIP events on the engine stream) vs the
                  fp32 MFMA peak 157.3 TFLOP/s (MI355X_MICROARCH.md).
@@ -47,8 +53,14 @@ from tools.bench_legs import (DAVIS_VAL_LENGTHS, FP32_MFMA_PEAK_TFLOPS, NOISE_X,
                               r2_roofline, real_inputs, ref_self_noise, roofline_objects, session_leg, session_parity)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (value repeats, power, rooflines, R2, davis-val, config 3, sessions, drivers, "
+                         "CPU baseline and parity legs, the determinism check, the gathered J&F rows); without it a run sets up, warms up, "
+                         "times --steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (the masks interact() returned) to DIR/<name>.npy, float32")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); default = WORLD_SIZE or 1")
     ap.add_argument("--steps", type=int, default=None, help="videos per rank (uniform workload, default 12) / samples of the whole job (davis-val, default 30)")
     ap.add_argument("--warmup", type=int, default=1)
@@ -96,7 +108,26 @@ def parse():
     ap.add_argument("--session-videos", type=int, default=4)
     ap.add_argument("--no-r2", dest="r2", action="store_false",
                     help="skip the extra R2 number (a second interaction: cached keys + fusion; reported, not the headline)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+DUMP_ELEMS = 12_000_000       # --dump-outputs: float32 elements over all arrays (48 MB)
+
+
+def dump_outputs(d, arrays):
+    """[(name, array)] -> d/<name>.npy in float32.  An array above its share of DUMP_ELEMS is replaced by a fixed seeded sample of its
+    elements (flattened, sorted indices; the same indices for every array of that size), so that two builds compare element for element."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_ELEMS // max(1, len(arrays))
+    picks = {}
+    for name, x in arrays:
+        x = np.asarray(x)
+        if x.size > share:
+            if x.size not in picks:
+                picks[x.size] = np.sort(np.random.default_rng(0).choice(x.size, share, replace=False))
+            x = x.reshape(-1)[picks[x.size]]
+        np.save(os.path.join(d, f"{name}.npy"), x.astype(np.float32))
+
 
 def launch_ranks(n):
     """`python bench.py --gpus N` outside torch.distributed.run: this process - which has not touched the GPU (no
@@ -116,6 +147,9 @@ def launch_ranks(n):
 
 def main():
     a = parse()
+    if not a.full:           # a plain run: no leg beside the headline (davis-val still runs when it IS the headline)
+        a.r2 = a.power = a.davis_val = a.config3 = a.memread_roofline = a.session = a.drivers = False
+        a.no_profile, a.value_repeats, a.cpu_frames = True, 1, 0
     if a.steps is None:
         a.steps = 12 if a.workload == "uniform" else len(DAVIS_VAL_LENGTHS)
     if a.gpus is not None and a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -282,13 +316,27 @@ def main():
     frames = sum(r[0] for r in res)
     l0 = next(l for l in range(S) if res[l][1] is not None)      # a lane that ran at least one video (lane 0 unless it lost every ticket)
     last = res[l0][1]
-    # determinism under concurrency: (i) repeated videos of one engine agreed bit for bit inside the timed region,
-    # (ii) that lane's last video, re-run now with nothing else in flight, reproduces its concurrent result
-    with torch.cuda.stream(streams[l0]):
-        e = pool[l0][res[l0][3]]
-        e.reset()
-        solo = e.interact(mask0, 0, scribble=K_OBJ > 1)
-    lanes_identical = all(repeats_identical(r[2]) for r in res) and np.array_equal(solo, last)
+    if a.dump_outputs and rank == 0 and a.workload == "uniform":
+        # the last video of every pooled engine (clip c = lane * per_lane + slot): which lane took which ticket varies from run to run,
+        # what an engine computes for its clip does not.  An engine that got no video in the timed region runs its clip once now.
+        latest = {(l, slot): o for l, r in enumerate(res) for slot, o in r[2]}
+        for l in range(S):
+            for j in range(per_lane):
+                if (l, j) not in latest:
+                    with torch.cuda.stream(streams[l]):
+                        pool[l][j].reset()
+                        latest[(l, j)] = pool[l][j].interact(mask0, 0, scribble=K_OBJ > 1)
+        dump_outputs(a.dump_outputs, [(f"masks_clip{l * per_lane + j}", latest[(l, j)]) for l in range(S) for j in range(per_lane)])
+        del latest
+    lanes_identical = None
+    if a.full:
+        # determinism under concurrency: (i) repeated videos of one engine agreed bit for bit inside the timed region,
+        # (ii) that lane's last video, re-run now with nothing else in flight, reproduces its concurrent result
+        with torch.cuda.stream(streams[l0]):
+            e = pool[l0][res[l0][3]]
+            e.reset()
+            solo = e.interact(mask0, 0, scribble=K_OBJ > 1)
+        lanes_identical = all(repeats_identical(r[2]) for r in res) and np.array_equal(solo, last)
     del res
 
     # The same timed region twice more (value_repeats): `value` stays the FIRST region - the contract's K steps - and the spread of
@@ -353,7 +401,11 @@ def main():
     torch.cuda.empty_cache()
     dv = None
     if (a.davis_val or a.workload == "davis-val") and real is None and K_OBJ == 1:
-        dv = davis_val_leg(prop, fuse, a, H, W, rank, world, local, streams, barrier, eo_main)
+        dv_masks = [] if (a.dump_outputs and rank == 0 and a.workload == "davis-val") else None
+        dv = davis_val_leg(prop, fuse, a, H, W, rank, world, local, streams, barrier, eo_main, keep=dv_masks)
+        if dv_masks is not None:                 # the headline's own samples (this rank's share of the LPT assignment)
+            dump_outputs(a.dump_outputs, [(f"masks_sample{i:02d}", m) for i, m in dv_masks])
+            del dv_masks
 
     # Extra leg: BASELINE config 3 at its stated size - one multi-object engine (k objects through the scribble /
     # (k+1)-channel path, the only multi-object path of the reference: inference_core.py:220-233), mem_freq = 1 (every
@@ -400,16 +452,17 @@ def main():
     else:
         dt_all, frames_all = dt, float(frames)
 
-    if dist is not None:                                  # repeats: every rank ran the same regions; whole-job rate = sum over ranks
+    if dist is not None and a.full:                       # repeats: every rank ran the same regions; whole-job rate = sum over ranks
         rr_t = torch.tensor(rep_rates, dtype=torch.float64, device=red_dev)
         dist.all_reduce(rr_t, op=dist.ReduceOp.SUM)
         rep_rates = [float(v) for v in rr_t.tolist()]
         rep_rates[0] = frames_all / dt_all                # the headline itself: frames of all ranks / the slowest rank's time
 
-    # per-video J&F rows of the last video of each rank, gathered once (the path's only exchange step)
-    sc = metrics.sequence_scores_gpu((gt[0, :, 0] > 0.5).cuda(), torch.from_numpy(last == 1).cuda())   # HIP J/F kernel
-    row = np.array([[rank, sc[1:, 0].mean(), sc[1:, 1].mean(), sc[1:, 2].mean()]], np.float32)
-    rows = shard.gather_rows(row, 4)
+    if a.full:
+        # per-video J&F rows of the last video of each rank, gathered once (the path's only exchange step)
+        sc = metrics.sequence_scores_gpu((gt[0, :, 0] > 0.5).cuda(), torch.from_numpy(last == 1).cuda())   # HIP J/F kernel
+        row = np.array([[rank, sc[1:, 0].mean(), sc[1:, 1].mean(), sc[1:, 2].mean()]], np.float32)
+        rows = shard.gather_rows(row, 4)
 
     if rank == 0:
         out = {
@@ -428,13 +481,6 @@ def main():
                        "clips": f"{S * per_lane} distinct synthetic clips (one per pooled engine)",
                        "weights": "model_weights/mivos/stcn.pth + fusion.pth" if real is not None else "synthetic recipe seed 0 (no checkpoints offline)"},
             "ms_per_frame": 1e3 * dt_all / (frames_all / world),
-            "jf_rows_rank_J_F_JF": rows.round(4).tolist(),
-            # the path's one exchange step really ran over every rank: rows the gather returned, and the backend that carried it ("nccl" = RCCL)
-            "ranks_seen": int(len(rows)), "backend": (dist.get_backend() if dist is not None else None),
-            "concurrent_videos_bit_identical": bool(lanes_identical),
-            "power": power,
-            "value_repeats": {"frames_per_s": [round(v, 2) for v in rep_rates], "min": min(rep_rates), "median": sorted(rep_rates)[len(rep_rates) // 2],
-                              "max": max(rep_rates), "what": "the timed region run back to back on this box; `value` is the first"},
             # rank 0's host side of the timed regions: what one lane's thread costs the host (8 ranks x (lanes + prefetch threads) share one host at N = 8)
             "host_enqueue_ms_per_video": 1e3 * host_acct["enqueue_s"] / max(host_acct["videos"], 1),
             "host_cpu_s_per_lane": [round(v, 3) for v in host_acct["lane_cpu_s"]],
@@ -444,6 +490,16 @@ def main():
             # download of every leg took the one-DMA path
             "pageable_downloads": __import__("eva_vos_amd.inference_core", fromlist=["x"]).pageable_downloads(),
         }
+        if a.full:
+            out.update({
+                "jf_rows_rank_J_F_JF": rows.round(4).tolist(),
+                # the path's one exchange step really ran over every rank: rows the gather returned, and the backend that carried it ("nccl" = RCCL)
+                "ranks_seen": int(len(rows)), "backend": (dist.get_backend() if dist is not None else None),
+                "concurrent_videos_bit_identical": bool(lanes_identical),
+                "power": power,
+                "value_repeats": {"frames_per_s": [round(v, 2) for v in rep_rates], "min": min(rep_rates), "median": sorted(rep_rates)[len(rep_rates) // 2],
+                                  "max": max(rep_rates), "what": "the timed region run back to back on this box; `value` is the first"},
+            })
         if r2 is not None:
             out["r2_frames_per_s_rank0"] = r2
         if r2_roof is not None:
@@ -457,7 +513,7 @@ def main():
                 out["config"]["sharding"] = f"LPT over {world} rank(s)"
         if prof is not None:
             out.update(roofline_objects(prof, roof_frames, t_roof, frames, dt_r1, a.roof_steps))
-        else:
+        elif a.full:
             out["roofline"] = None
         if cfg3 is not None:
             out["config3"] = cfg3
@@ -474,7 +530,7 @@ def main():
                 out["parity_long_clip"] = long_clip_parity(prop, fuse, psd, fsd, H, W, a.parity_long_frames, a.mem_freq, eo_main)
             if a.parity_session_rounds > 0 and real is None:
                 out["parity_session"] = session_parity(prop, fuse, psd, fsd, H, W, a.parity_session_frames, a.parity_session_rounds, a.mem_freq, eo_main)
-        else:
+        elif a.full:
             out["cpu_baseline"] = None
             out["cpu_baseline_note"] = ("the CPU oracle is timed on rank 0 at N=1 only (task contract); see the N=1 line" if world > 1
                                         else "skipped (--cpu-frames 0)")

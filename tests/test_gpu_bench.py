@@ -13,7 +13,7 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-SMALL = ["--steps", "2", "--warmup", "0", "--frames", "12", "--height", "240", "--width", "432", "--streams", "1",
+SMALL = ["--full", "--steps", "2", "--warmup", "0", "--frames", "12", "--height", "240", "--width", "432", "--streams", "1",
          "--no-profile", "--no-r2", "--cpu-frames", "0", "--no-config3", "--no-memread-roofline", "--no-davis-val", "--no-drivers", "--no-session", "--no-power"]
 
 
@@ -58,6 +58,39 @@ def test_gpus_flag_launches_that_many_ranks():
     assert two["concurrent_videos_bit_identical"]
 
 
+PLAIN = ["--steps", "3", "--warmup", "1", "--frames", "12", "--height", "240", "--width", "432", "--streams", "2"]
+
+
+def test_plain_run_times_the_steps_only_and_dumps_its_outputs(tmp_path):
+    """Without --full a run is the headline alone: --steps timed steps, no leg beside them.  --dump-outputs writes the masks the timed
+    steps returned (one file per pooled engine, float32, 64 MB at most), the same on every run with the same arguments - also for an
+    engine that got no step (3 steps over 2 lanes x 2 engines).  With --workload davis-val the headline's own samples are written."""
+    import numpy as np
+    runs = [run_bench(["--gpus", "1"] + PLAIN + ["--dump-outputs", str(tmp_path / f"out{i}")]) for i in range(2)]
+    one = runs[0]
+    assert all(k in one for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert one["steps"] == 3 and one["value"] > 0 and one["dtype"] == "f32"
+    frames = one["value"] * one["ms_per_step"] * 1e-3 * one["steps"]
+    assert abs(frames - 3 * 11) < 1e-6 * frames + 1e-3, "ms_per_step x steps is the timed region of 3 videos x 11 frames"
+    for k in ("value_repeats", "power", "roofline", "roofline_r2", "r2_frames_per_s_rank0", "davis_val", "config3", "roofline_memread",
+              "session", "drivers", "cpu_baseline", "parity_vs_cpu_oracle", "jf_rows_rank_J_F_JF", "concurrent_videos_bit_identical"):
+        assert k not in one, k
+    names = sorted(os.listdir(tmp_path / "out0"))
+    assert names == sorted(os.listdir(tmp_path / "out1")) == [f"masks_clip{c}.npy" for c in range(4)]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "out0" / n), np.load(tmp_path / "out1" / n)
+        assert a.dtype == np.float32 and a.shape == (12, 240, 432) and np.array_equal(a, b), n
+        assert set(np.unique(a).tolist()) <= {0.0, 1.0} and a.any(), n
+        total += a.nbytes
+    assert total <= 64e6
+    dv = run_bench(["--gpus", "1", "--steps", "4", "--warmup", "0", "--frames", "12", "--height", "240", "--width", "432", "--streams", "2",
+                    "--workload", "davis-val", "--davis-max-frames", "9", "--dump-outputs", str(tmp_path / "dv")])
+    assert dv["scaling"] == "strong" and dv["steps"] == 4 and dv["davis_val"]["samples"] == 4 and "value_repeats" not in dv
+    assert sorted(os.listdir(tmp_path / "dv")) == [f"masks_sample{i:02d}.npy" for i in range(4)]
+    assert all(np.load(tmp_path / "dv" / f"masks_sample{i:02d}.npy").shape == (9, 240, 432) for i in range(4))
+
+
 def test_davis_val_workload_is_sharded_by_lpt_over_the_ranks():
     """--workload davis-val: the whole job runs --steps samples with the DAVIS-2017-val lengths (clamped here so that the
     test stays small), assigned to the ranks by LPT; fixed total work -> "strong"; every sample is processed exactly once."""
@@ -80,7 +113,7 @@ def test_davis_val_workload_is_sharded_by_lpt_over_the_ranks():
     assert max(dv["rank_busy_fraction"]) == 1.0 and dv["imbalance_max_over_mean_frames"] < 1.2
 
 
-TINY = ["--warmup", "0", "--frames", "5", "--height", "128", "--width", "160", "--streams", "1", "--no-profile", "--no-r2",
+TINY = ["--full", "--warmup", "0", "--frames", "5", "--height", "128", "--width", "160", "--streams", "1", "--no-profile", "--no-r2",
         "--cpu-frames", "0", "--no-config3", "--no-memread-roofline", "--no-drivers", "--no-session", "--no-power"]
 
 

@@ -516,7 +516,7 @@ def r2_roofline(prop, fuse, img, mask0, mask_mid, T, mem_freq, scribble):
     return res
 
 
-def davis_val_leg(prop, fuse, a, H, W, rank, world, local, streams, barrier, eo=None):
+def davis_val_leg(prop, fuse, a, H, W, rank, world, local, streams, barrier, eo=None, keep=None):
     """samples with the 30 DAVIS-2017-val sequence lengths, assigned to the ranks by LPT on their
     frame counts (eva_vos_amd.shard.lpt_assign; the reference slices by --min-idx/--max-idx, eval_annotation_method.py:34-35,
     113-119), inside a rank to the in-flight lanes the same way.  Fixed total work -> strong scaling: frames of ALL samples /
@@ -566,6 +566,8 @@ def davis_val_leg(prop, fuse, a, H, W, rank, world, local, streams, barrier, eo=
     t_rank = time.perf_counter() - t0
     barrier()
     rows = shard.gather_rows(np.array([[rank, t_rank, sum(frames), len(mine)]], np.float64), 4)
+    if keep is not None:                                     # bench.py --dump-outputs: the masks interact() returned, by sample
+        keep.extend((i, engines[i].np_masks) for i in sorted(engines))
     engines.clear()
     torch.cuda.empty_cache()
     t_max = float(rows[:, 1].max())

@@ -13,7 +13,7 @@ python tools/dual_sweep_ab.py 2>&1 | grep -v amdgpu.ids | tee $O/dual_sweep_ab.t
 echo "--- driver lanes + host account"
 python tools/driver_lanes.py 8 40 2>&1 | grep -v amdgpu.ids | tee $O/driver_lanes.txt
 echo "--- bench (sessions + drivers only)"
-python bench.py --steps 8 --cpu-frames 0 --no-config3 --no-memread-roofline --no-davis-val --no-power --value-repeats 1 > $O/bench_short.json 2> $O/bench_short.err
+python bench.py --full --steps 8 --cpu-frames 0 --no-config3 --no-memread-roofline --no-davis-val --no-power --value-repeats 1 > $O/bench_short.json 2> $O/bench_short.err
 python - <<PY
 import json
 d = json.loads([l for l in open("$O/bench_short.json") if l.startswith("{")][-1])

@@ -8,10 +8,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof_final
 rm -rf $O; mkdir -p $O
 cd $R
-SECONDS=0; python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench_default wall ${SECONDS} s" | tee $O/bench_default.wall
-python bench.py --streams 1 --cpu-frames 0 --no-profile --no-r2 --no-config3 --no-memread-roofline --no-davis-val --no-drivers --no-session --no-power 2>/dev/null | tail -1 > $O/bench_streams1.json
+SECONDS=0; python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench_default wall ${SECONDS} s" | tee $O/bench_default.wall
+python bench.py --full --streams 1 --cpu-frames 0 --no-profile --no-r2 --no-config3 --no-memread-roofline --no-davis-val --no-drivers --no-session --no-power 2>/dev/null | tail -1 > $O/bench_streams1.json
 cd /tmp && export TMPDIR=/tmp
-Q="--cpu-frames 0 --no-r2 --no-config3 --no-memread-roofline --no-davis-val --no-drivers --no-session --no-power --value-repeats 1"
+Q="--full --cpu-frames 0 --no-r2 --no-config3 --no-memread-roofline --no-davis-val --no-drivers --no-session --no-power --value-repeats 1"
 STCN_LOOKAHEAD=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o r -- python3 $R/bench.py --streams 1 --steps 2 --warmup 1 --no-profile $Q > $O/trace.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_default -o r -- python3 $R/bench.py $Q > $O/trace_default.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_memread -o r -- python3 $R/tools/memread_bench.py --k 5 > $O/trace_memread.log 2>&1
