@@ -756,7 +756,17 @@ static Plan plan_variant(const ConvP &p, bool big, int force_splitk, size_t ws_f
     return best;
 }
 
-void conv_plan(ConvP &p, int force_splitk, size_t ws_floats) {
+// which instance conv_launch takes for this (planned) conv - reported to the tests through stcn_last_conv_path()
+static const char *conv_variant_name(const ConvP &p) {
+    const bool narrow = narrow_variant(p), big = p.tile_big != 0, smallc = smallc_variant(p);
+    if (p.chain) return "direct_pointwise_chain";
+    if (p.pointwise && !big && !narrow && !smallc) return "direct_pointwise";
+    if (big) return "direct_big";
+    if (narrow) return smallc ? "direct_narrow_smallc" : "direct_narrow";
+    return smallc ? "direct_smallc" : "direct";
+}
+
+void conv_plan(ConvP &p, int force_splitk, size_t ws_floats, ConvPlan &cp) {
     static const int big_mode = [] { const char *e = getenv("STCN_CONV_BIG"); return e ? atoi(e) : 1; }();
     Plan pl = plan_variant(p, false, force_splitk, ws_floats);
     constexpr int big_mink = 2304;               // smallest padded K for the 128x128 instance (1x1 convs measured no gain from it)
@@ -774,6 +784,11 @@ void conv_plan(ConvP &p, int force_splitk, size_t ws_floats) {
     if (dbg)
         fprintf(stderr, "conv_plan M=%d N=%d K=%d: %s splitk=%d tail=(%d full, %d pieces of %d) cost %.0f\n", p.M, p.N, p.Kp,
                 pl.big ? "128x128" : (narrow_variant(p) ? "128x32" : "64x64"), pl.splitk, pl.rem_full, pl.rem_split, pl.rem_per, pl.cost);
+    cp.family = CONV_DIRECT;
+    cp.variant = conv_variant_name(p);
+    cp.splitk = p.splitk; cp.tail = p.rem_split > 1;
+    cp.n_in = 0; cp.n_gemm = 1; cp.reduce = p.splitk > 1 || p.rem_split > 1;
+    cp.fl_exec = cp.fl;
 }
 
 // dynamic LDS above 64 KB has to be opted into once per (device, kernel function): a process may hold models on several
@@ -789,16 +804,6 @@ void allow_big_lds(const void *kernel, size_t lds) {
         (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
-// which instance conv_launch takes for this (planned) conv - reported to the tests through stcn_last_conv_path()
-const char *conv_variant_name(const ConvP &p) {
-    const bool narrow = narrow_variant(p), big = p.tile_big != 0, smallc = smallc_variant(p);
-    if (p.chain) return "direct_pointwise_chain";
-    if (p.pointwise && !big && !narrow && !smallc) return "direct_pointwise";
-    if (big) return "direct_big";
-    if (narrow) return smallc ? "direct_narrow_smallc" : "direct_narrow";
-    return smallc ? "direct_smallc" : "direct";
-}
-
 void conv_launch(const ConvP &p, hipStream_t s, hipEvent_t *ev_gemm, hipEvent_t *ev_red) {
     const bool narrow = narrow_variant(p), big = p.tile_big != 0;
     const int BM = narrow ? 128 : (big ? 128 : 64), BN = narrow ? 32 : (big ? 128 : 64);
@@ -812,50 +817,34 @@ void conv_launch(const ConvP &p, hipStream_t s, hipEvent_t *ev_gemm, hipEvent_t 
     const bool smallc = smallc_variant(p);
     const int pn = p.panel;
     const TileDiv td{fastdiv_make((unsigned)ntile), fastdiv_make((unsigned)tiles_n), fastdiv_make((unsigned)(tiles_m * (pn > 0 ? pn : 1))), tiles_m};
-    hipEvent_t e0 = ev_gemm ? ev_gemm[0] : nullptr, e1 = ev_gemm ? ev_gemm[1] : nullptr;
     if (p.chain) {                                        // pointwise chain: nt consecutive tiles per workgroup, one resident set of workgroups
         const dim3 cgrid((unsigned)((ntile + p.chain - 1) / p.chain));
-        if (p.relu_in) {
-            if (e0) hipExtLaunchKernelGGL(pw_chain_kernel<true>, cgrid, dim3(256), lds, s, e0, e1, 0, p, tiles_n, ntile, p.chain, td);
-            else hipLaunchKernelGGL(pw_chain_kernel<true>, cgrid, dim3(256), lds, s, p, tiles_n, ntile, p.chain, td);
-        } else {
-            if (e0) hipExtLaunchKernelGGL(pw_chain_kernel<false>, cgrid, dim3(256), lds, s, e0, e1, 0, p, tiles_n, ntile, p.chain, td);
-            else hipLaunchKernelGGL(pw_chain_kernel<false>, cgrid, dim3(256), lds, s, p, tiles_n, ntile, p.chain, td);
-        }
+        launch(p.relu_in ? pw_chain_kernel<true> : pw_chain_kernel<false>, cgrid, dim3(256), lds, s, ev_gemm, p, tiles_n, ntile, p.chain, td);
         return;
     }
-    {
-#define STCN_LAUNCH(WM_, WN_, RM_, RN_, SC_, RL_, ...)                                                                  \
-    do {                                                                                                                 \
-        auto kfn = conv_gemm_kernel<WM_, WN_, RM_, RN_, SC_, RL_, ##__VA_ARGS__>;                                        \
-        allow_big_lds(reinterpret_cast<const void *>(kfn), lds);                                                         \
-        if (e0) hipExtLaunchKernelGGL(kfn, grid, dim3(256), lds, s, e0, e1, 0, p, tiles_n, ntile, per, td);              \
-        else hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s, p, tiles_n, ntile, per, td);                               \
-    } while (0)
+#define STCN_INST(WM_, WN_, RM_, RN_, SC_, RL_, ...) kfn = conv_gemm_kernel<WM_, WN_, RM_, RN_, SC_, RL_, ##__VA_ARGS__>
+    auto STCN_INST(2, 2, 1, 1, false, false);
     const bool pw = p.pointwise && !big && !narrow && !smallc;
     const int key = (pw ? 16 : 0) | (big ? 8 : 0) | (narrow ? 4 : 0) | (smallc ? 2 : 0) | (p.relu_in ? 1 : 0);
     switch (key) {
-        case 16: STCN_LAUNCH(2, 2, 1, 1, false, false, true); break;
-        case 17: STCN_LAUNCH(2, 2, 1, 1, false, true, true); break;
-        case 0: STCN_LAUNCH(2, 2, 1, 1, false, false); break;
-        case 1: STCN_LAUNCH(2, 2, 1, 1, false, true); break;
-        case 2: STCN_LAUNCH(2, 2, 1, 1, true, false); break;
-        case 3: STCN_LAUNCH(2, 2, 1, 1, true, true); break;
-        case 4: STCN_LAUNCH(4, 1, 1, 1, false, false); break;
-        case 5: STCN_LAUNCH(4, 1, 1, 1, false, true); break;
-        case 6: STCN_LAUNCH(4, 1, 1, 1, true, false); break;
-        case 7: STCN_LAUNCH(4, 1, 1, 1, true, true); break;
-        case 8: STCN_LAUNCH(2, 2, 2, 2, false, false); break;
-        default: STCN_LAUNCH(2, 2, 2, 2, false, true); break;
+        case 16: STCN_INST(2, 2, 1, 1, false, false, true); break;
+        case 17: STCN_INST(2, 2, 1, 1, false, true, true); break;
+        case 0: break;
+        case 1: STCN_INST(2, 2, 1, 1, false, true); break;
+        case 2: STCN_INST(2, 2, 1, 1, true, false); break;
+        case 3: STCN_INST(2, 2, 1, 1, true, true); break;
+        case 4: STCN_INST(4, 1, 1, 1, false, false); break;
+        case 5: STCN_INST(4, 1, 1, 1, false, true); break;
+        case 6: STCN_INST(4, 1, 1, 1, true, false); break;
+        case 7: STCN_INST(4, 1, 1, 1, true, true); break;
+        case 8: STCN_INST(2, 2, 2, 2, false, false); break;
+        default: STCN_INST(2, 2, 2, 2, false, true); break;
     }
-    }
-#undef STCN_LAUNCH
+#undef STCN_INST
+    launch(kfn, grid, dim3(256), lds, s, ev_gemm, p, tiles_n, ntile, per, td);
     if (tail) {
         const unsigned blocks = (unsigned)((ntile - p.rem_full) * (BM * BN / 1024));
-        if (ev_red)
-            hipExtLaunchKernelGGL(conv_reduce_tiles_kernel, dim3(blocks), dim3(256), 0, s, ev_red[0], ev_red[1], 0, p, tiles_n, ntile, BM, BN, td);
-        else
-            hipLaunchKernelGGL(conv_reduce_tiles_kernel, dim3(blocks), dim3(256), 0, s, p, tiles_n, ntile, BM, BN, td);
+        launch(conv_reduce_tiles_kernel, dim3(blocks), dim3(256), 0, s, ev_red, p, tiles_n, ntile, BM, BN, td);
     } else if (p.splitk > 1) {
         conv_reduce_launch(p, s, ev_red);
     }
@@ -865,10 +854,7 @@ void conv_reduce_launch(const ConvP &p, hipStream_t s, hipEvent_t *ev_red) {
     const long total4 = (long)p.M * p.N / 4;
     long blocks = (total4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    if (ev_red)
-        hipExtLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ev_red[0], ev_red[1], 0, p);
-    else
-        hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    launch(conv_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ev_red, p);
 }
 
 // ------------------------------------------------------------------------------------------------

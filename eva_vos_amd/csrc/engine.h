@@ -17,11 +17,15 @@ namespace stcn {
 void set_error(const char *fmt, ...);
 struct Model;
 struct ConvW;
-// builds the Winograd weights of a stride-1-capable 3x3 conv from its repacked fp32 host weights (no-op when not eligible)
 // engine buffers come from a per-device pool (engine.cpp: a hipFree per buffer synchronises the device and stalls the other lanes)
 hipError_t pool_malloc(void **p, size_t bytes);
 void pool_free(void *p);
 void pool_release();
+// does a conv of this shape get Winograd weights (make_wino / make_wino4 / make_wino_fusion12 below)?
+bool wants_wino(const ConvW &cw);
+bool wants_wino4(const ConvW &cw);
+bool wants_wino_fusion12(const ConvW &cw);
+// builds the Winograd weights of a stride-1-capable 3x3 conv from its repacked fp32 host weights (no-op when not eligible)
 int make_wino(Model &m, ConvW &cw, const std::vector<float> &w_host);
 // F(4x4,3x3) weights of a decoder-side 3x3 conv (no-op when not eligible)
 int make_wino4(Model &m, ConvW &cw, const std::vector<float> &w_host);
@@ -76,7 +80,7 @@ struct Prof {
     std::vector<hipEvent_t> pool;
     void reset();
     void begin(int cls, hipStream_t s);
-    // register an event pair that the launch itself will fill (hipExtLaunchKernelGGL); null when off
+    // register an event pair that the launch itself will fill (launch() in kernels.h); null when off
     hipEvent_t *attach(int cls, bool hbm_bound_conv = false);
     // conv launches below the machine balance (HBM-bound), also counted in the STCN_K_CONV totals
     double hbm_conv_flops = 0, hbm_conv_bytes = 0, hbm_conv_ms = 0; int hbm_conv_launches = 0;
@@ -116,14 +120,35 @@ struct Work {
 // ---- stages (enqueue only) -----------------------------------------------------------------
 struct KeyOut { float *k16, *msq, *f16_thin, *f16, *s8, *s4, *f8_copy, *f4_copy, *dthin = nullptr, *cthin = nullptr; };
 void inject_failure_after(int n);        // tests: the n-th launch_status() of this thread fails
-int launch_status(const char *what);
+int launch_status(const char *what);     // STCN_OK, or STCN_E_HIP with the failing launch class in the error string
 const char *last_conv_path();            // kernel family of this thread's last run_conv ("wino4 chunks=2", "direct_pointwise splitk=1", ...)
 void set_conv_path(const char *s);
 void conv_trace(int on);                 // tests: log "name=path" of every conv this thread enqueues
-const char *conv_trace_get();     // STCN_OK, or STCN_E_HIP with the failing launch class in the error string
-int run_conv(const Model &m, Work &w, hipStream_t s, const char *name, const float *x0, int c0, long bs0,
-             const float *x1, int c1, long bs1, int B, int H, int W, int stride, float *y, long y_bs,
-             const float *res, long res_bs, int relu_in, int relu_out, int force_splitk = 0, int res_bmod = 0);
+const char *conv_trace_get();
+// ---- one convolution: what a call sets, by name
+// Batch strides are in elements.  CONV_DENSE: densely packed ([B][H][W][C] input, [B][OH][OW][Cout] residual), worked out by plan_conv.
+// A zero stride means a BROADCAST over the batch for an input or the residual, and a dense tensor for the output.
+constexpr long CONV_DENSE = -1;
+struct ConvArgs {
+    const float *x0 = nullptr, *x1 = nullptr;       // input = channel concat of up to two sources
+    int c0 = 0, c1 = 0;
+    long bs0 = CONV_DENSE, bs1 = 0;
+    int B = 1, H = 0, W = 0, stride = 1;
+    float *y = nullptr; long y_bs = 0;
+    const float *res = nullptr; long res_bs = CONV_DENSE; int res_bmod = 0;   // res_bmod: see ConvP
+    int relu_in = 0, relu_out = 0, force_splitk = 0;
+    ConvArgs(const float *x, int c, int B_, int H_, int W_, long bs = CONV_DENSE) : x0(x), c0(c), bs0(bs), B(B_), H(H_), W(W_) {}
+    ConvArgs &concat(const float *x, int c, long bs) { x1 = x; c1 = c; bs1 = bs; return *this; }
+    ConvArgs &strided(int s) { stride = s; return *this; }
+    ConvArgs &out(float *y_, long bs = 0) { y = y_; y_bs = bs; return *this; }
+    ConvArgs &residual(const float *r, long bs = CONV_DENSE, int bmod = 0) { res = r; res_bs = bs; res_bmod = bmod; return *this; }
+    ConvArgs &relu(int in, int out_) { relu_in = in; relu_out = out_; return *this; }
+    ConvArgs &splitk(int k) { force_splitk = k; return *this; }
+};
+// the planning half of run_conv (pure host code): ConvP of layer `name` over a, and the plan of the family that takes it
+int plan_conv(const Model &m, const Work &w, const std::string &name, const ConvArgs &a, ConvP &p, ConvPlan &pl);
+const char *format_conv_path(const ConvPlan &pl, char *out, size_t n);
+int run_conv(const Model &m, Work &w, hipStream_t s, const std::string &name, const ConvArgs &a);
 // B consecutive frames at once; outputs of frame b at o.<ptr> + b * out_bs
 int encode_key(const Model &m, Work &w, hipStream_t s, const float *img4, const KeyOut &o, int B = 1, long out_bs = 0);
 // vd / vc: cached frame-only halves of fuser.block1 (nullptr: compute the full two-source convs)

@@ -317,16 +317,25 @@ __global__ __launch_bounds__(256, 2) void fusion_wino_kernel(const float *__rest
 
 // conv1 (9 -> 12 channels in HBM, 16 per tap here: a quarter of its MFMAs multiply zeros) measured 53 us on this kernel, 49 us
 // on the generic one: off by default (STCN_FUSION_CONV12=1 switches it on; the instance stays tested)
-bool fusion_conv_winograd(const ConvP &p) { return (p.Cin == 32 || p.Cin == 12) && p.wino_u && p.kn.fusion_wino; }
+static bool fusion_conv_winograd(const ConvP &p) { return (p.Cin == 32 || p.Cin == 12) && p.wino_u && p.kn.fusion_wino; }
 
-bool fusion_conv_eligible(const ConvP &p) {
+static bool fusion_conv_eligible(const ConvP &p) {
     constexpr bool on = true;
     return on && p.N == 32 && p.KH == 3 && p.KW == 3 && p.stride == 1 && p.B == 1 && !p.x1 && !p.relu_in &&
            (p.Cin == 32 || (p.Cin == 12 && (p.kn.fusion_conv12 || fusion_conv_winograd(p)))) &&
            p.K == 9 * p.Cin && (p.y_bs == 0) && (!p.res || !p.res_bmod) && p.bias;
 }
 
-void fusion_conv_launch(const ConvP &p, hipStream_t s, hipEvent_t *ev) {
+bool fusion_conv_plan(const ConvP &p, ConvPlan &pl) {
+    if (!fusion_conv_eligible(p)) return false;
+    pl.family = CONV_FUSION;
+    pl.fusion_wino = fusion_conv_winograd(p);
+    pl.n_in = 0; pl.n_gemm = 1; pl.reduce = false;
+    pl.fl_exec = pl.fusion_wino ? 2.0 * 16.0 * ((p.H + 3) / 4 * 2) * (double)((p.W + 31) / 32 * 16) * ((p.Cin + 7) / 8 * 8) * p.N : pl.fl;
+    return true;
+}
+
+void fusion_conv_launch(const ConvP &p, const ConvPlan &pl, hipStream_t s, hipEvent_t *ev) {
     constexpr int PH = 4;
     const int tiles_x = (p.W + 31) / 32, tiles_y = (p.H + PH - 1) / PH, n_patches = tiles_x * tiles_y;
     static const int resident = [] {                  // two workgroups per CU (206 VGPRs: two waves per SIMD)
@@ -336,39 +345,27 @@ void fusion_conv_launch(const ConvP &p, hipStream_t s, hipEvent_t *ev) {
         return 2 * (cus > 0 ? cus : 256);
     }();
     const dim3 grid((unsigned)(n_patches < resident ? n_patches : resident));
-    if (fusion_conv_winograd(p)) {
+    if (pl.fusion_wino) {
         const size_t ldsw = (size_t)((PH + 2) * 34 * ((p.Cin + 7) / 8 * 8 + 4) + 4 * 2 * 32 * 32) * sizeof(float);
-#define STCN_FW(RL_, RS_)                                                                                                          \
-    do {                                                                                                                          \
-        if (p.Cin == 12) STCN_FW2(12, RL_, RS_); else STCN_FW2(32, RL_, RS_);                                                     \
-    } while (0)
-#define STCN_FW2(CIN_, RL_, RS_)                                                                                                   \
-    do {                                                                                                                          \
-        auto kfn = fusion_wino_kernel<CIN_, RL_, RS_>;                                                                            \
-        if (ev) hipExtLaunchKernelGGL(kfn, grid, dim3(256), ldsw, s, ev[0], ev[1], 0, p.x0, p.wino_u, p.bias, p.res, p.y, p.H, p.W, tiles_x, n_patches); \
-        else hipLaunchKernelGGL(kfn, grid, dim3(256), ldsw, s, p.x0, p.wino_u, p.bias, p.res, p.y, p.H, p.W, tiles_x, n_patches);  \
-    } while (0)
+#define STCN_FW(RL_, RS_) (p.Cin == 12 ? fusion_wino_kernel<12, RL_, RS_> : fusion_wino_kernel<32, RL_, RS_>)
+        auto kfn = STCN_FW(false, false);
         switch ((p.relu_out ? 2 : 0) | (p.res ? 1 : 0)) {
-            case 0: STCN_FW(false, false); break;
-            case 1: STCN_FW(false, true); break;
-            case 2: STCN_FW(true, false); break;
-            default: STCN_FW(true, true); break;
+            case 0: break;
+            case 1: kfn = STCN_FW(false, true); break;
+            case 2: kfn = STCN_FW(true, false); break;
+            default: kfn = STCN_FW(true, true); break;
         }
 #undef STCN_FW
-#undef STCN_FW2
+        launch(kfn, grid, dim3(256), ldsw, s, ev, p.x0, p.wino_u, p.bias, p.res, p.y, p.H, p.W, tiles_x, n_patches);
         return;
     }
     const int cinp = (p.Cin + 7) / 8 * 8;
     const size_t lds = (size_t)2 * (PH + 2) * 34 * (cinp + 4) * sizeof(float);
-#define STCN_FC(CIN_, RL_, RS_)                                                                                                   \
-    do {                                                                                                                          \
-        auto kfn = fusion_conv_kernel<CIN_, PH, RL_, RS_>;                                                                        \
-        if (ev) hipExtLaunchKernelGGL(kfn, grid, dim3(256), lds, s, ev[0], ev[1], 0, p.x0, p.w, p.Kp, p.bias, p.res, p.y, p.H, p.W, tiles_x, n_patches); \
-        else hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s, p.x0, p.w, p.Kp, p.bias, p.res, p.y, p.H, p.W, tiles_x, n_patches); \
-    } while (0)
+#define STCN_FC(CIN_, RL_, RS_) kfn = fusion_conv_kernel<CIN_, PH, RL_, RS_>
+    auto STCN_FC(32, false, false);
     const int key = (p.Cin == 12 ? 4 : 0) | (p.relu_out ? 2 : 0) | (p.res ? 1 : 0);
     switch (key) {
-        case 0: STCN_FC(32, false, false); break;
+        case 0: break;
         case 1: STCN_FC(32, false, true); break;
         case 2: STCN_FC(32, true, false); break;
         case 3: STCN_FC(32, true, true); break;
@@ -378,6 +375,7 @@ void fusion_conv_launch(const ConvP &p, hipStream_t s, hipEvent_t *ev) {
         default: STCN_FC(12, true, true); break;
     }
 #undef STCN_FC
+    launch(kfn, grid, dim3(256), lds, s, ev, p.x0, p.w, p.Kp, p.bias, p.res, p.y, p.H, p.W, tiles_x, n_patches);
 }
 
 }  // namespace stcn

@@ -23,6 +23,43 @@ struct DevBuf {
     int alloc(size_t floats) { HIPCHK(hipMalloc((void **)&p, floats * 4)); return STCN_OK; }
     ~DevBuf() { if (p) { (void)hipDeviceSynchronize(); (void)hipFree(p); } }
 };
+// the one-layer model of the conv hooks: layer "t", weights not yet bound
+ConvW test_convw(int Cin, int Cout, int KH, int KW) {
+    ConvW cw;
+    cw.cout = Cout; cw.cin = Cin; cw.cin_p = Cin; cw.kh = KH; cw.kw = KW;
+    cw.K = KH * KW * Cin; cw.Kp = (cw.K + 31) / 32 * 32;
+    return cw;
+}
+// V of either Winograd form: 16 positions x tiles of 2x2 padded to 64, or 36 positions x tiles of 4x4 padded to 128 (for a
+// handful of tiles the padded F(4x4) workspace is the larger one - sized for F(2x2) alone such a case fell back silently)
+size_t test_wino_v_floats(int B, int OH, int OW, int Cin) {
+    const size_t v2 = (size_t)16 * Cin * (((size_t)B * ((OH + 1) / 2) * ((OW + 1) / 2) + 63) / 64 * 64);
+    const size_t v4 = (size_t)36 * Cin * (((size_t)B * ((OH + 3) / 4) * ((OW + 3) / 4) + 127) / 128 * 128);
+    return v2 > v4 ? v2 : v4;
+}
+// the one-layer model (layer "t") and workspace stcn_test_conv / stcn_bench_conv run.  hw: host copy of the weights [Cout][Kp] of a
+// stride-1 3x3 conv - it gets the Winograd weights the engine would make (f4: as a decoder layer) and a V workspace - else null
+struct ConvRig {
+    Model m;
+    Work w;
+    DevBuf wv, ws;
+    ~ConvRig() { (void)hipDeviceSynchronize(); for (void *p : m.allocs) (void)hipFree(p); }
+    int init(ConvW cw, const std::vector<float> *hw, bool f4, int B, int OH, int OW, size_t slab_floats) {
+        if (hw) {
+            RC(make_wino(m, cw, *hw));
+            RC(make_wino_fusion12(m, cw, *hw));
+            if (f4) RC(make_wino4(m, cw, *hw));
+            w.wino_v_floats = test_wino_v_floats(B, OH, OW, cw.cin_p);
+            RC(wv.alloc(w.wino_v_floats));
+            w.wino_v = wv.p;
+        }
+        m.conv["t"] = cw;
+        w.splitk_floats = slab_floats;
+        RC(ws.alloc(w.splitk_floats));
+        w.splitk = ws.p;
+        return STCN_OK;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -31,38 +68,23 @@ int stcn_test_conv(void *stream, const float *x, const float *wgt, const float *
                    int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int flags, int splitk) {
     if (Cin % 4 || pad != KH / 2 || KH != KW) { set_error("stcn_test_conv: Cin%%4==0, square kernel, pad=K/2 required"); return STCN_E_INVALID; }
     hipStream_t s = (hipStream_t)stream;
-    Model m;
-    ConvW cw;
-    cw.cout = Cout; cw.cin = Cin; cw.cin_p = Cin; cw.kh = KH; cw.kw = KW;
-    cw.K = KH * KW * Cin; cw.Kp = (cw.K + 31) / 32 * 32;
-    DevBuf wpad, ws;
+    ConvW cw = test_convw(Cin, Cout, KH, KW);
+    DevBuf wpad;
     RC(wpad.alloc((size_t)Cout * cw.Kp));
     HIPCHK(hipMemsetAsync(wpad.p, 0, (size_t)Cout * cw.Kp * 4, s));
     HIPCHK(hipMemcpy2DAsync(wpad.p, (size_t)cw.Kp * 4, wgt, (size_t)cw.K * 4, (size_t)cw.K * 4, Cout, hipMemcpyDeviceToDevice, s));
     cw.w = wpad.p; cw.bias = const_cast<float *>(bias);
-    struct Guard { Model &m; ~Guard() { (void)hipDeviceSynchronize(); for (void *p : m.allocs) (void)hipFree(p); } } guard{m};
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    Work w;
-    DevBuf wv;
-    if (KH == 3 && stride == 1) {          // stride-1 3x3: the Winograd path, as in the engine
+    const bool wino = KH == 3 && stride == 1;          // stride-1 3x3: the Winograd path, as in the engine
+    std::vector<float> hw;
+    if (wino) {
         HIPCHK(hipStreamSynchronize(s));
-        std::vector<float> hw((size_t)Cout * cw.Kp);
+        hw.resize((size_t)Cout * cw.Kp);
         HIPCHK(hipMemcpy(hw.data(), wpad.p, hw.size() * 4, hipMemcpyDeviceToHost));
-        RC(make_wino(m, cw, hw));
-        RC(make_wino_fusion12(m, cw, hw));
-        if (flags & 4) { RC(make_wino4(m, cw, hw)); m.wino4_min_wg = 0; }        // flags bit 2: as a decoder layer (F(4x4,3x3))
-        // V of either Winograd form: 16 positions x tiles of 2x2 padded to 64, or 36 positions x tiles of 4x4 padded to 128 (for a
-        // handful of tiles the padded F(4x4) workspace is the larger one - sized for F(2x2) alone such a case fell back silently)
-        const size_t v2 = (size_t)16 * Cin * (((size_t)B * ((OH + 1) / 2) * ((OW + 1) / 2) + 63) / 64 * 64);
-        const size_t v4 = (size_t)36 * Cin * (((size_t)B * ((OH + 3) / 4) * ((OW + 3) / 4) + 127) / 128 * 128);
-        w.wino_v_floats = v2 > v4 ? v2 : v4;
-        RC(wv.alloc(w.wino_v_floats));
-        w.wino_v = wv.p;
     }
-    m.conv["t"] = cw;
-    w.splitk_floats = (size_t)16 * 1024 * 1024;
-    RC(ws.alloc(w.splitk_floats));
-    w.splitk = ws.p;
+    ConvRig r;
+    RC(r.init(cw, wino ? &hw : nullptr, flags & 4, B, OH, OW, (size_t)16 * 1024 * 1024));    // flags bit 2: as a decoder layer (F(4x4,3x3))
+    if (wino && (flags & 4)) r.m.wino4_min_wg = 0;
     if (Cout == 1) {
         if (stride != 1) { set_error("Cout==1 path is stride 1"); return STCN_E_INVALID; }
         float b0 = 0.f;
@@ -70,11 +92,37 @@ int stcn_test_conv(void *stream, const float *x, const float *wgt, const float *
         conv_n1_launch(x, wpad.p, b0, y, B, H, W, Cin, KH, flags & 1, s);
         set_conv_path("n1");
     } else {
-        RC(run_conv(m, w, s, "t", x, Cin, (long)H * W * Cin, nullptr, 0, 0, B, H, W, stride, y, 0, res, (long)OH * OW * Cout,
-                    flags & 1, (flags >> 1) & 1, splitk));
+        RC(run_conv(r.m, r.w, s, "t", ConvArgs(x, Cin, B, H, W).strided(stride).out(y).residual(res).relu(flags & 1, (flags >> 1) & 1).splitk(splitk)));
     }
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
+// The plan stcn_test_conv's conv would take, as its path string: the same ConvW and Work sizes, but nothing is allocated on a device
+// and nothing is launched (works without a GPU).  The planners test wino_u, wino4_u, partial, bias and res for null only, so one
+// non-null constant stands in for every buffer.  No residual.
+int stcn_test_conv_path(int B, int H, int W, int Cin, int Cout, int K, int stride, int flags, int splitk, char *out, int n) {
+    if (Cin % 4 || !out || n < 1) { set_error("stcn_test_conv_path: Cin%%4==0 and an output buffer required"); return STCN_E_INVALID; }
+    static float buf[4];
+    Model m;
+    ConvW cw = test_convw(Cin, Cout, K, K);
+    cw.w = cw.bias = buf;
+    const int OH = (H + 2 * (K / 2) - K) / stride + 1, OW = (W + 2 * (K / 2) - K) / stride + 1;
+    Work w;
+    if (K == 3 && stride == 1) {
+        if (wants_wino(cw) || wants_wino_fusion12(cw)) cw.wino_u = buf;
+        if (flags & 4) { if (wants_wino4(cw)) cw.wino4_u = buf; m.wino4_min_wg = 0; }
+        w.wino_v_floats = test_wino_v_floats(B, OH, OW, Cin);
+        w.wino_v = buf;
+    }
+    m.conv["t"] = cw;
+    w.splitk_floats = (size_t)16 * 1024 * 1024;
+    w.splitk = buf;
+    ConvP p;
+    ConvPlan pl;
+    RC(plan_conv(m, w, "t", ConvArgs(buf, Cin, B, H, W).strided(stride).out(buf).relu(flags & 1, (flags >> 1) & 1).splitk(splitk), p, pl));
+    format_conv_path(pl, out, (size_t)n);
     return STCN_OK;
 }
 
@@ -82,12 +130,9 @@ int stcn_bench_conv(void *stream, int B, int H, int W, int Cin, int Cout, int KH
                     int iters, float *avg_ms, double *flops_per_launch) {
     hipStream_t s = (hipStream_t)stream;
     (void)pad;
-    Model m;
-    ConvW cw;
-    cw.cout = Cout; cw.cin = Cin; cw.cin_p = Cin; cw.kh = KH; cw.kw = KW;
-    cw.K = KH * KW * Cin; cw.Kp = (cw.K + 31) / 32 * 32;
+    ConvW cw = test_convw(Cin, Cout, KH, KW);
     const int OH = (H + 2 * (KH / 2) - KH) / stride + 1, OW = (W + 2 * (KW / 2) - KW) / stride + 1;
-    DevBuf x, wt, b, y, ws;
+    DevBuf x, wt, b, y;
     RC(x.alloc((size_t)B * H * W * Cin)); RC(wt.alloc((size_t)Cout * cw.Kp)); RC(b.alloc(Cout));
     RC(y.alloc((size_t)B * OH * OW * Cout));
     // non-trivial data (zero operands raise the clock: cdna_hip_programming.md rule 25)
@@ -101,35 +146,19 @@ int stcn_bench_conv(void *stream, int B, int H, int W, int Cin, int Cout, int KH
     HIPCHK(hipMemcpy(wt.p, h.data(), h.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemsetAsync(b.p, 0, Cout * 4, s));
     cw.w = wt.p; cw.bias = b.p;
-    struct Guard { Model &m; ~Guard() { (void)hipDeviceSynchronize(); for (void *p : m.allocs) (void)hipFree(p); } } guard{m};
-    Work w;
-    DevBuf wv;
-    if (KH == 3 && stride == 1) {
-        RC(make_wino(m, cw, h));
-        RC(make_wino_fusion12(m, cw, h));
-        if (getenv("STCN_BENCH_CONV_F4")) RC(make_wino4(m, cw, h));              // time the layer as a decoder layer
-        // V of either Winograd form: 16 positions x tiles of 2x2 padded to 64, or 36 positions x tiles of 4x4 padded to 128 (for a
-        // handful of tiles the padded F(4x4) workspace is the larger one - sized for F(2x2) alone such a case fell back silently)
-        const size_t v2 = (size_t)16 * Cin * (((size_t)B * ((OH + 1) / 2) * ((OW + 1) / 2) + 63) / 64 * 64);
-        const size_t v4 = (size_t)36 * Cin * (((size_t)B * ((OH + 3) / 4) * ((OW + 3) / 4) + 127) / 128 * 128);
-        w.wino_v_floats = v2 > v4 ? v2 : v4;
-        RC(wv.alloc(w.wino_v_floats));
-        w.wino_v = wv.p;
-    }
-    m.conv["t"] = cw;
-    w.splitk_floats = (size_t)32 * 1024 * 1024;
-    RC(ws.alloc(w.splitk_floats));
-    w.splitk = ws.p;
+    ConvRig r;                                                    // STCN_BENCH_CONV_F4: time the layer as a decoder layer
+    RC(r.init(cw, KH == 3 && stride == 1 ? &h : nullptr, getenv("STCN_BENCH_CONV_F4") != nullptr, B, OH, OW, (size_t)32 * 1024 * 1024));
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     DevBuf resb;                                                  // STCN_BENCH_CONV_RES=1: with a residual operand (the ResNet conv3 layers)
     const long obs = (long)OH * OW * Cout;
     if (getenv("STCN_BENCH_CONV_RES")) { RC(resb.alloc((size_t)B * obs)); HIPCHK(hipMemsetAsync(resb.p, 0, (size_t)B * obs * 4, s)); }
+    const ConvArgs args = ConvArgs(x.p, Cin, B, H, W).strided(stride).out(y.p).residual(resb.p).relu(0, 1).splitk(splitk);
     for (int i = 0; i < 3; ++i)
-        RC(run_conv(m, w, s, "t", x.p, Cin, (long)H * W * Cin, nullptr, 0, 0, B, H, W, stride, y.p, 0, resb.p, resb.p ? obs : 0, 0, 1, splitk));
+        RC(run_conv(r.m, r.w, s, "t", args));
     HIPCHK(hipEventRecord(e0, s));
     for (int i = 0; i < iters; ++i)
-        RC(run_conv(m, w, s, "t", x.p, Cin, (long)H * W * Cin, nullptr, 0, 0, B, H, W, stride, y.p, 0, resb.p, resb.p ? obs : 0, 0, 1, splitk));
+        RC(run_conv(r.m, r.w, s, "t", args));
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0.f;
@@ -246,8 +275,9 @@ int stcn_test_decode(const stcn_model *m, void *stream, const float *readout, co
     const Dims &d = t.w.d;
     DevBuf s8, s4;
     RC(s8.alloc((size_t)d.hw8 * 512)); RC(s4.alloc((size_t)d.hw4 * 256));
-    RC(run_conv(m->m, t.w, s, "decoder.up_16_8.skip_conv", f8, 512, 0, nullptr, 0, 0, 1, d.h8, d.w8, 1, s8.p, 0, nullptr, 0, 0, 0));
-    RC(run_conv(m->m, t.w, s, "decoder.up_8_4.skip_conv", f4, 256, 0, nullptr, 0, 0, 1, d.h4, d.w4, 1, s4.p, 0, nullptr, 0, 0, 0));
+    // one frame as a broadcast source (batch stride 0), as the hook always ran these two
+    RC(run_conv(m->m, t.w, s, "decoder.up_16_8.skip_conv", ConvArgs(f8, 512, 1, d.h8, d.w8, 0).out(s8.p)));
+    RC(run_conv(m->m, t.w, s, "decoder.up_8_4.skip_conv", ConvArgs(f4, 256, 1, d.h4, d.w4, 0).out(s4.p)));
     RC(decode(m->m, t.w, s, readout, f16_thin, s8.p, s4.p, agg, d.npix));
     if (logit4) HIPCHK(hipMemcpyAsync(logit4, t.w.logit4, (size_t)k * d.hw4 * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));

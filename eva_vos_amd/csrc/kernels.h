@@ -90,20 +90,40 @@ struct ConvP {
     int chain;              // > 0: pointwise chain kernel, this many consecutive tiles per workgroup (conv_plan)
     Knobs kn;               // the workspace's snapshot of the launch-level tunables
 };
-// fills the launch plan of p (tile variant, split-K or tail balancing); force_splitk > 0 pins a plain split-K;
-// workspace_floats = capacity of p.partial
-void conv_plan(ConvP &p, int force_splitk, size_t workspace_floats);
-// ev_gemm / ev_red: optional {start, stop} event pairs attached to the GEMM / reduce dispatches themselves
-// (hipExtLaunchKernelGGL: kernel begin/end timestamps, no extra barrier packets)
+// ---------------------------------------------------------------- the plan of one convolution
+// Filled ONCE per run_conv call (engine.cpp plan_conv) by the planning function of the family that takes the conv; the accounting, the
+// profiling event pairs, the path string of the tests and the family's launch function all read this one object - nothing plans again.
+constexpr int W4_MAX_CHUNKS = 16;       // most slices of a chunked F(4x4) launch (wino4_plan); one profiling event pair per slice
+// launch plan of the F(4x4) GEMM: 64- or 32-tile workgroups, and (32-tile only) the tail split
+struct W4Plan { int Mt, Mt_pad, tiles_m, tiles_n, mb, grid, full_wg, pieces, per, chunks, tm_per_chunk; };
+enum ConvFamily { CONV_LITERAL = 0, CONV_FUSION = 1, CONV_WINO4 = 2, CONV_WINO2 = 3, CONV_DIRECT = 4 };
+struct ConvPlan {
+    int family = CONV_LITERAL;
+    bool fusion_wino = false;       // CONV_FUSION: Winograd F(2x2,3x3) inside the workgroup (else the direct FusionNet kernel)
+    W4Plan w4{};                    // CONV_WINO4
+    int splitk = 1;                 // CONV_WINO2: split-K of the Winograd GEMM; CONV_DIRECT: p.splitk
+    int ppw = 0;                    // CONV_WINO2: GEMM instance (positions per wave)
+    const char *variant = "";       // CONV_DIRECT: conv_variant_name() (the tile plan itself is in ConvP: the kernels read it)
+    bool tail = false;              // CONV_DIRECT: tail balancing (p.rem_split > 1)
+    size_t v_floats = 0;            // Winograd families: V workspace floats
+    int n_in = 0, n_gemm = 1;       // input-transform / GEMM launches (the chunks of an F(4x4) launch)
+    bool reduce = false;            // a reduce launch follows
+    double fl = 0;                  // algorithmic FLOP (set before the family plans)
+    double fl_exec = 0;             // FLOP the matrix cores execute (Winograd: fewer)
+};
+// Per family one planning function (true when the family takes p, its part of pl filled) and one launch function, which takes that plan
+// and does not plan.  ev_*: optional {start, stop} event pairs attached to the dispatches themselves (launch(): kernel begin/end
+// timestamps, no extra barrier packets).
+// direct implicit GEMM (always eligible): fills the launch plan of p (tile variant, split-K or tail balancing); force_splitk > 0 pins
+// a plain split-K; workspace_floats = capacity of p.partial
+void conv_plan(ConvP &p, int force_splitk, size_t workspace_floats, ConvPlan &pl);
 void conv_launch(const ConvP &p, hipStream_t s, hipEvent_t *ev_gemm = nullptr, hipEvent_t *ev_red = nullptr);
-const char *conv_variant_name(const ConvP &p);     // the conv_gemm_kernel instance a planned conv takes ("direct", "direct_pointwise", ...)
 // split-K tail of a conv whose slabs p.partial [p.splitk][M][N] are filled: sum + bias / residual / ReLU -> y
 void conv_reduce_launch(const ConvP &p, hipStream_t s, hipEvent_t *ev_red = nullptr);
-// Winograd F(2x2,3x3) path (winograd.hip): V workspace floats this conv needs, or 0 when it is not eligible
-size_t wino_workspace_floats(const ConvP &p);
-void wino_launch(const ConvP &p, float *V, size_t slab_floats, hipStream_t s, hipEvent_t *ev_in = nullptr, hipEvent_t *ev_gemm = nullptr,
+// Winograd F(2x2,3x3) path (winograd.hip): not eligible, or V needs more than v_cap floats -> false.  slab_floats = capacity of p.partial
+bool wino_plan(const ConvP &p, size_t v_cap, size_t slab_floats, ConvPlan &pl);
+void wino_launch(const ConvP &p, const ConvPlan &pl, float *V, hipStream_t s, hipEvent_t *ev_in = nullptr, hipEvent_t *ev_gemm = nullptr,
                  hipEvent_t *ev_red = nullptr);
-int wino_plan_splitk(const ConvP &p, size_t slab_floats);
 void wino_transform_weights(const float *w, int N, int Cin, int Kp, float *U);
 // fewest input channels of an F(4x4) layer.  64 (8 k-blocks, one K piece) since round 5: the 64-channel 3x3 convs of the value encoder's
 // ResNet-18 layer1 over the objects of a multi-object engine (129 600 rows at k = 5) take 56 instead of 98 us each - config 3 219 -> 224 frames/s;
@@ -112,21 +132,21 @@ void wino_transform_weights(const float *w, int N, int Cin, int Kp, float *U);
 #ifndef W4_MIN_CIN
 #define W4_MIN_CIN 64
 #endif
-// Winograd F(4x4,3x3) path (winograd4.hip, decoder layers): V workspace floats, or 0 when not eligible / fewer than min_wg workgroups
-size_t wino4_workspace_floats(const ConvP &p, int min_wg);
-// ev_in / ev_gemm: one {start, stop} pair per chunk (wino4_chunks: the transform and the GEMM alternate over slices of the tiles
+// Winograd F(4x4,3x3) path (winograd4.hip, decoder layers): not eligible, fewer than min_wg workgroups, or V needs more than v_cap floats -> false
+bool wino4_plan(const ConvP &p, int min_wg, size_t v_cap, size_t slab_floats, ConvPlan &pl);
+// ev_in / ev_gemm: one {start, stop} pair per chunk (pl.w4.chunks: the transform and the GEMM alternate over slices of the tiles
 // when V would not stay in the memory-side cache)
-void wino4_launch(const ConvP &p, float *V, size_t slab_floats, hipStream_t s, hipEvent_t *const *ev_in = nullptr,
+void wino4_launch(const ConvP &p, const ConvPlan &pl, float *V, hipStream_t s, hipEvent_t *const *ev_in = nullptr,
                   hipEvent_t *const *ev_gemm = nullptr, hipEvent_t *ev_red = nullptr);
-int wino4_chunks(const ConvP &p, size_t slab_floats);
-// does wino4_launch cut the last round of this conv's workgroups into K pieces (a reduce launch follows)?
-bool wino4_tail_split(const ConvP &p, size_t slab_floats);
 void wino4_transform_weights(const float *w, int N, int Cin, int Kp, float *U);
+// The family switches, read once per process: STCN_WINOGRAD (0: no F(2x2) weights, workspace or launches) and STCN_WINO4
+// (0 off, 1 on for flagged layers with enough workgroups (default), 2 whenever the shape allows)
+bool wino_enabled();
+int wino4_mode();
 
 // FusionNet convs (fusion_conv.hip): 3x3, stride 1, Cout = 32, Cin = 32 or 12, one dense image: weights in registers, patch in LDS
-bool fusion_conv_eligible(const ConvP &p);
-bool fusion_conv_winograd(const ConvP &p);      // an eligible conv runs as Winograd F(2x2,3x3) inside the workgroup (32 -> 32 layers)
-void fusion_conv_launch(const ConvP &p, hipStream_t s, hipEvent_t *ev_gemm = nullptr);
+bool fusion_conv_plan(const ConvP &p, ConvPlan &pl);
+void fusion_conv_launch(const ConvP &p, const ConvPlan &pl, hipStream_t s, hipEvent_t *ev_gemm = nullptr);
 
 // Cout == 1 convolution (decoder.pred, FusionNet.final_conv): one dot product per output pixel.
 // x [B,H,W,C] (C multiple of 4), w [KH*KW*C], y [B*H*W]; stride 1, "same" padding.
@@ -187,6 +207,16 @@ size_t memread_list_pairs(int Q);
 struct MemReadScratch { float *cand_v; int32_t *cand_i; int32_t *cand_n; float *gmax; float *tau; };
 // dynamic LDS above 64 KB has to be opted into once per (device, kernel function)
 void allow_big_lds(const void *kernel, size_t lds);
+#if defined(__HIPCC__)
+// The one way the conv families launch a kernel.  ev: {start, stop} event pair that the dispatch itself fills (profiling on), or null -
+// then a plain launch: the engine is launch-bound and an unprofiled launch must ask the runtime for nothing more than that.
+template <typename... KArgs, typename... Args>
+static inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, hipEvent_t *ev, const Args &...args) {
+    if (lds_bytes > 64 * 1024) allow_big_lds(reinterpret_cast<const void *>(kernel), lds_bytes);
+    if (ev) hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, s, ev[0], ev[1], 0, args...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
+}
+#endif
 // mk [N,64], msq [N] (+ >= 64 readable floats of padding), qk [Q,64]; mv [k][N][512] with object stride mv_os; readout [k][Q][512] with
 // object stride ro_os.  topk_idx/topk_w optional outputs [Q,50].
 void memory_read_launch(const float *mk, const float *msq, const float *qk, int N, int Q,

@@ -295,13 +295,13 @@ __global__ __launch_bounds__(1024 / PPW) void wino_gemm_kernel(const WinoG p, co
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static bool wino_enabled() {
+bool wino_enabled() {
     static const bool on = [] { const char *e = getenv("STCN_WINOGRAD"); return !e || atoi(e) != 0; }();
     return on;
 }
 
 // floats of V workspace the Winograd path needs for this conv (0: not eligible)
-size_t wino_workspace_floats(const ConvP &p) {
+static size_t wino_workspace_floats(const ConvP &p) {
     if (!wino_enabled() || !p.wino_u || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.x1) return 0;
     if (p.Cin % 32 || p.Cin < p.kn.wino_min_cin || p.N % WN || p.bs0 == 0) return 0;
     const long Mt = (long)p.B * ((p.OH + 1) / 2) * ((p.OW + 1) / 2);
@@ -318,7 +318,7 @@ size_t wino_workspace_floats(const ConvP &p) {
 
 // split-K of the Winograd GEMM: with few (tile, channel) workgroups the input channels are cut so that about one round of
 // CUs is busy; the pieces write transformed partial sums into the slabs of conv_reduce_kernel
-int wino_plan_splitk(const ConvP &p, size_t slab_floats) {
+static int wino_splitk(const ConvP &p, size_t slab_floats) {
     const int TH = (p.OH + 1) / 2, TW = (p.OW + 1) / 2;
     const int Mt_pad = (p.B * TH * TW + WT - 1) / WT * WT, KB = p.Cin / 8;
     const int ntile = (Mt_pad / WT) * (p.N / WN);
@@ -334,9 +334,24 @@ int wino_plan_splitk(const ConvP &p, size_t slab_floats) {
     return (KB + per - 1) / per;
 }
 
-// Winograd launch of a conv that wino_workspace_floats() accepted; V >= that many floats.  ev: optional {start, stop} pairs for
-// the transform, GEMM and reduce dispatches.  Returns the split-K factor used.
-void wino_launch(const ConvP &p, float *V, size_t slab_floats, hipStream_t s, hipEvent_t *ev_in, hipEvent_t *ev_gemm, hipEvent_t *ev_red) {
+bool wino_plan(const ConvP &p, size_t v_cap, size_t slab_floats, ConvPlan &pl) {
+    const size_t need = wino_workspace_floats(p);
+    if (need == 0 || need > v_cap) return false;
+    pl.family = CONV_WINO2;
+    pl.v_floats = need;
+    pl.splitk = wino_splitk(p, slab_floats);
+    // 16 waves x 1 position (4 waves per SIMD) feed the matrix pipe a little better on the short-K layers (+1.5-3 % up to 512
+    // input channels); with 1024+ channels the 8-wave form with its deeper per-wave prefetch is as good or better
+    const int ppw_env = p.kn.wino_ppw;                    // tests run every shape under both instances
+    pl.ppw = ppw_env == 1 || ppw_env == 2 ? ppw_env : (p.Cin <= 512 ? 1 : 2);
+    pl.n_in = 1; pl.n_gemm = 1; pl.reduce = pl.splitk > 1;
+    pl.fl_exec = 2.0 * (double)(need / p.Cin) * p.Cin * p.N;
+    return true;
+}
+
+// Winograd launch of a conv that wino_plan() accepted; V >= pl.v_floats floats.  ev: optional {start, stop} pairs for
+// the transform, GEMM and reduce dispatches.
+void wino_launch(const ConvP &p, const ConvPlan &pl, float *V, hipStream_t s, hipEvent_t *ev_in, hipEvent_t *ev_gemm, hipEvent_t *ev_red) {
     const int TH = (p.OH + 1) / 2, TW = (p.OW + 1) / 2;
     const int Mt = p.B * TH * TW, Mt_pad = (Mt + WT - 1) / WT * WT, KB = p.Cin / 8;
     // ---- input transform: 8 threads per tile, the 32-channel blocks cut into chunks so that the grid fills the chip
@@ -347,12 +362,7 @@ void wino_launch(const ConvP &p, float *V, size_t slab_floats, hipStream_t s, hi
         chunks = chunks < 1 ? 1 : (chunks > NCB ? NCB : chunks);
         const int per = (NCB + chunks - 1) / chunks;
         chunks = (NCB + per - 1) / per;
-        if (ev_in)
-            hipExtLaunchKernelGGL(wino_input_kernel, dim3(gx, chunks), dim3(256), 0, s, ev_in[0], ev_in[1], 0, p.x0, p.bs0, p.H, p.W, p.Cin,
-                                  p.relu_in, TH, TW, Mt, Mt_pad, per, V);
-        else
-            hipLaunchKernelGGL(wino_input_kernel, dim3(gx, chunks), dim3(256), 0, s, p.x0, p.bs0, p.H, p.W, p.Cin, p.relu_in, TH, TW, Mt,
-                               Mt_pad, per, V);
+        launch(wino_input_kernel, dim3(gx, chunks), dim3(256), 0, s, ev_in, p.x0, p.bs0, p.H, p.W, p.Cin, p.relu_in, TH, TW, Mt, Mt_pad, per, V);
     }
     // ---- GEMM
     WinoG g{};
@@ -365,27 +375,12 @@ void wino_launch(const ConvP &p, float *V, size_t slab_floats, hipStream_t s, hi
     const int tiles_m = Mt_pad / WT, tiles_n = p.N / WN, ntile = tiles_m * tiles_n;
     g.fd_tpi = fastdiv_make((unsigned)(TH * TW)); g.fd_tw = fastdiv_make((unsigned)TW);
     g.fd_ntile = fastdiv_make((unsigned)ntile); g.fd_tiles_n = fastdiv_make((unsigned)tiles_n);
-    const int sk = wino_plan_splitk(p, slab_floats);
+    const int sk = pl.splitk;
     g.kb_per_split = (KB + sk - 1) / sk;
     g.splitk = sk; g.partial = p.partial;
     const size_t lds = (size_t)16 * WT * 32 * sizeof(float);
-    // 16 waves x 1 position (4 waves per SIMD) feed the matrix pipe a little better on the short-K layers (+1.5-3 % up to 512
-    // input channels); with 1024+ channels the 8-wave form with its deeper per-wave prefetch is as good or better
-    const int ppw_env = p.kn.wino_ppw;                    // tests run every shape under both instances
-    const int ppw = ppw_env == 1 || ppw_env == 2 ? ppw_env : (p.Cin <= 512 ? 1 : 2);
-    if (ppw == 1) {
-        allow_big_lds(reinterpret_cast<const void *>(&wino_gemm_kernel<1>), lds);
-        if (ev_gemm)
-            hipExtLaunchKernelGGL(wino_gemm_kernel<1>, dim3(ntile * sk), dim3(1024), lds, s, ev_gemm[0], ev_gemm[1], 0, g, tiles_n, ntile);
-        else
-            hipLaunchKernelGGL(wino_gemm_kernel<1>, dim3(ntile * sk), dim3(1024), lds, s, g, tiles_n, ntile);
-    } else {
-        allow_big_lds(reinterpret_cast<const void *>(&wino_gemm_kernel<2>), lds);
-        if (ev_gemm)
-            hipExtLaunchKernelGGL(wino_gemm_kernel<2>, dim3(ntile * sk), dim3(512), lds, s, ev_gemm[0], ev_gemm[1], 0, g, tiles_n, ntile);
-        else
-            hipLaunchKernelGGL(wino_gemm_kernel<2>, dim3(ntile * sk), dim3(512), lds, s, g, tiles_n, ntile);
-    }
+    if (pl.ppw == 1) launch(wino_gemm_kernel<1>, dim3(ntile * sk), dim3(1024), lds, s, ev_gemm, g, tiles_n, ntile);
+    else launch(wino_gemm_kernel<2>, dim3(ntile * sk), dim3(512), lds, s, ev_gemm, g, tiles_n, ntile);
     if (sk > 1) {
         ConvP q = p;
         q.splitk = sk;

@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void wino4_reduce_kernel(const Wino4G p, const
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int wino4_mode() {          // 0 off, 1 on for flagged layers with enough workgroups (default), 2 whenever the shape allows
+int wino4_mode() {                 // 0 off, 1 on for flagged layers with enough workgroups (default), 2 whenever the shape allows
     static const int m = [] { const char *e = getenv("STCN_WINO4"); return e ? atoi(e) : 1; }();
     return m;
 }
@@ -512,7 +512,7 @@ static int wino4_small_pieces(int grid, int KB) {
 }
 
 // floats of V workspace the F(4x4) path needs for this conv (0: not eligible).  min_wg: fewest workgroups worth launching
-size_t wino4_workspace_floats(const ConvP &p, int min_wg) {
+static size_t wino4_workspace_floats(const ConvP &p, int min_wg) {
     if (!wino4_mode() || !p.wino4_u || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.x1) return 0;
     if (p.Cin % 32 || p.Cin < W4_MIN_CIN || p.N % W4N || p.bs0 == 0) return 0;
     const long Mt = (long)p.B * ((p.OH + 3) / 4) * ((p.OW + 3) / 4);
@@ -527,8 +527,7 @@ size_t wino4_workspace_floats(const ConvP &p, int min_wg) {
 }
 
 // launch plan of the F(4x4) GEMM: 64- or 32-tile workgroups, and (32-tile only) the tail split
-struct W4Plan { int Mt, Mt_pad, tiles_m, tiles_n, mb, grid, full_wg, pieces, per, chunks, tm_per_chunk; };
-static W4Plan wino4_plan(const ConvP &p, size_t slab_floats) {
+static W4Plan wino4_gemm_plan(const ConvP &p, size_t slab_floats) {
     static const int mb_env = [] { const char *e = getenv("STCN_WINO4_MB"); return e ? atoi(e) : 0; }();
     static const bool tail_on = [] { const char *e = getenv("STCN_WINO4_TAIL"); return !e || atoi(e) != 0; }();
     const int cus = wino4_cus();
@@ -581,16 +580,24 @@ static W4Plan wino4_plan(const ConvP &p, size_t slab_floats) {
         const int rpc = (rounds + n - 1) / n;
         int tmpc = rpc * cus / pl.tiles_n;
         tmpc = tmpc < 1 ? 1 : tmpc;
-        if (tmpc < pl.tiles_m && (pl.tiles_m + tmpc - 1) / tmpc <= 16) { pl.tm_per_chunk = tmpc; pl.chunks = (pl.tiles_m + tmpc - 1) / tmpc; }
+        if (tmpc < pl.tiles_m && (pl.tiles_m + tmpc - 1) / tmpc <= W4_MAX_CHUNKS) { pl.tm_per_chunk = tmpc; pl.chunks = (pl.tiles_m + tmpc - 1) / tmpc; }
     }
     return pl;
 }
-int wino4_chunks(const ConvP &p, size_t slab_floats) { return wino4_plan(p, slab_floats).chunks; }
-bool wino4_tail_split(const ConvP &p, size_t slab_floats) { return wino4_plan(p, slab_floats).pieces > 1; }
+bool wino4_plan(const ConvP &p, int min_wg, size_t v_cap, size_t slab_floats, ConvPlan &cp) {
+    const size_t need = wino4_workspace_floats(p, min_wg);
+    if (need == 0 || need > v_cap) return false;
+    cp.family = CONV_WINO4;
+    cp.v_floats = need;
+    cp.w4 = wino4_gemm_plan(p, slab_floats);
+    cp.n_in = cp.n_gemm = cp.w4.chunks; cp.reduce = cp.w4.pieces > 1;
+    cp.fl_exec = 2.0 * (double)need * p.N;
+    return true;
+}
 
-void wino4_launch(const ConvP &p, float *V, size_t slab_floats, hipStream_t s, hipEvent_t *const *ev_in, hipEvent_t *const *ev_gemm,
+void wino4_launch(const ConvP &p, const ConvPlan &cp, float *V, hipStream_t s, hipEvent_t *const *ev_in, hipEvent_t *const *ev_gemm,
                   hipEvent_t *ev_red) {
-    const W4Plan pl = wino4_plan(p, slab_floats);
+    const W4Plan &pl = cp.w4;
     const int TH = (p.OH + 3) / 4, TW = (p.OW + 3) / 4;
     const int Mt = pl.Mt, Mt_pad = pl.Mt_pad, KB = p.Cin / 8;
     Wino4G g{};
@@ -630,33 +637,16 @@ void wino4_launch(const ConvP &p, float *V, size_t slab_floats, hipStream_t s, h
             chunks = chunks < 1 ? 1 : (chunks > NCB ? NCB : chunks);
             const int per = (NCB + chunks - 1) / chunks;
             chunks = (NCB + per - 1) / per;
-            if (ei)
-                hipExtLaunchKernelGGL(wino4_input_kernel, dim3(gx, chunks), dim3(256), 0, s, ei[0], ei[1], 0, p.x0, p.x0_bytes, p.bs0, p.H, p.W,
-                                      p.Cin, p.relu_in, TH, TW, Mt, Mt_pad, per, tile_lo, tile_hi, V);
-            else
-                hipLaunchKernelGGL(wino4_input_kernel, dim3(gx, chunks), dim3(256), 0, s, p.x0, p.x0_bytes, p.bs0, p.H, p.W, p.Cin, p.relu_in, TH,
-                                   TW, Mt, Mt_pad, per, tile_lo, tile_hi, V);
+            launch(wino4_input_kernel, dim3(gx, chunks), dim3(256), 0, s, ei, p.x0, p.x0_bytes, p.bs0, p.H, p.W, p.Cin, p.relu_in, TH, TW, Mt,
+                   Mt_pad, per, tile_lo, tile_hi, V);
         }
         g.tm0 = tm_lo;
         if (mb == 2) {
             const int grid = (tm_hi - tm_lo) * tiles_n;
-            allow_big_lds(reinterpret_cast<const void *>(&wino4_gemm_kernel<2>), lds);
-            if (eg)
-                hipExtLaunchKernelGGL(wino4_gemm_kernel<2>, dim3(grid), dim3(64 * W4W), lds, s, eg[0], eg[1], 0, g, tiles_n);
-            else
-                hipLaunchKernelGGL(wino4_gemm_kernel<2>, dim3(grid), dim3(64 * W4W), lds, s, g, tiles_n);
+            launch(wino4_gemm_kernel<2>, dim3(grid), dim3(64 * W4W), lds, s, eg, g, tiles_n);
         } else {
-            allow_big_lds(reinterpret_cast<const void *>(&wino4_gemm_kernel<1>), lds);
-            if (eg)
-                hipExtLaunchKernelGGL(wino4_gemm_kernel<1>, dim3(pl.grid), dim3(64 * W4W), lds, s, eg[0], eg[1], 0, g, tiles_n);
-            else
-                hipLaunchKernelGGL(wino4_gemm_kernel<1>, dim3(pl.grid), dim3(64 * W4W), lds, s, g, tiles_n);
-            if (g.pieces > 1) {
-                if (ev_red)
-                    hipExtLaunchKernelGGL(wino4_reduce_kernel, dim3((tiles_m * tiles_n - g.full_wg) * 64), dim3(256), 0, s, ev_red[0], ev_red[1], 0, g, tiles_n);
-                else
-                    hipLaunchKernelGGL(wino4_reduce_kernel, dim3((tiles_m * tiles_n - g.full_wg) * 64), dim3(256), 0, s, g, tiles_n);
-            }
+            launch(wino4_gemm_kernel<1>, dim3(pl.grid), dim3(64 * W4W), lds, s, eg, g, tiles_n);
+            if (g.pieces > 1) launch(wino4_reduce_kernel, dim3((tiles_m * tiles_n - g.full_wg) * 64), dim3(256), 0, s, ev_red, g, tiles_n);
         }
     }
 }

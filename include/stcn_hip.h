@@ -141,6 +141,9 @@ int stcn_test_conv(void *stream, const float *x, const float *w, const float *bi
                    float *y, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                    int pad, int flags, int splitk);
 
+/* Test hook: the kernel family and plan stcn_test_conv would run this shape as (the string stcn_last_conv_path() gives after it), from
+ * the host-side planners alone: nothing is allocated on a device, nothing is launched, no GPU is needed.  out: n bytes. */
+int stcn_test_conv_path(int B, int H, int W, int Cin, int Cout, int K, int stride, int flags, int splitk, char *out, int n);
 /* Which kernel family the calling thread's last convolution (stcn_test_conv, or the last conv an interact() enqueued) ran as:
  * "direct splitk=1", "direct_pointwise splitk=1", "direct_narrow ...", "direct_smallc ...", "direct_big ...", "... +tail ...",
  * "wino2 ppw=1 splitk=2" (Winograd F(2x2,3x3)), "wino4 chunks=2 +tail" (F(4x4,3x3)), "fusion_wino", "fusion_direct", "n1".
