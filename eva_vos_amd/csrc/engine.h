@@ -88,6 +88,8 @@ struct Prof {
     void end(hipStream_t s);
     int collect(float *ms);
     ~Prof();
+private:
+    Ev &push_pair(int cls, bool hbm);           // appends an event pair (from the pool, else created) to events
 };
 
 // scratch for one in-flight frame computation (sized for nh x nw and k objects)
@@ -149,6 +151,18 @@ struct ConvArgs {
 int plan_conv(const Model &m, const Work &w, const std::string &name, const ConvArgs &a, ConvP &p, ConvPlan &pl);
 const char *format_conv_path(const ConvPlan &pl, char *out, size_t n);
 int run_conv(const Model &m, Work &w, hipStream_t s, const std::string &name, const ConvArgs &a);
+// ---- one sweep of do_pass: its schedule, as data
+// The frames strictly between idx and closest, visited away from idx (direction = sign of closest - idx), cut into decode groups.  A frame is
+// inserted into the memory bank when it is not the sweep's last and lies >= mem_freq frames from the last inserted one (from idx before the
+// first insertion); a group ends at an inserting frame, at `cap` frames, or with the sweep.  Pure host code: no engine state, no HIP call.
+struct SweepGroup {
+    int first;        // first frame in sweep order
+    int t_lo;         // lowest frame (== first in a forward sweep)
+    int G;            // frames
+    bool inserts;     // the group's last frame in sweep order goes into the bank (no other frame of a group ever does)
+};
+std::vector<SweepGroup> plan_sweep(int idx, int closest, int mem_freq, int cap);
+constexpr int MAX_DECODE_GROUP = 8;      // the largest cap an engine uses
 // B consecutive frames at once; outputs of frame b at o.<ptr> + b * out_bs
 int encode_key(const Model &m, Work &w, hipStream_t s, const float *img4, const KeyOut &o, int B = 1, long out_bs = 0);
 // vd / vc: cached frame-only halves of fuser.block1 (nullptr: compute the full two-source convs)
@@ -215,7 +229,7 @@ struct stcn_engine {
     char fuse_pending[2] = {0, 0};       // ev_fuse[b] is recorded and the main stream has not waited for it yet
     int agg_buf = 0;
     int key_batch = 1;                   // frames per key-encoder pass (env STCN_KEY_BATCH)
-    int group = 1;                       // frames per memory-read + decoder pass (env STCN_DECODE_BATCH, k == 1)
+    int group = 1;                       // frames per memory-read + decoder pass (env STCN_DECODE_BATCH), <= MAX_DECODE_GROUP
     stcn::Prof prof;
     stcn_stats stats{};
     std::string failed;                  // non-empty: a failed interaction left prob / masks half-written (see stcn_interact)

@@ -258,6 +258,18 @@ int stcn_bench_memory_read(void *stream, const float *mk, const float *mv, const
     return STCN_OK;
 }
 
+int stcn_test_sweep_plan(int idx, int closest, int mem_freq, int cap, int32_t *out, int n, int32_t *count) {
+    if (mem_freq < 1 || cap < 1 || n < 0 || (n > 0 && !out) || !count) { set_error("stcn_test_sweep_plan: bad arguments"); return STCN_E_INVALID; }
+    const std::vector<SweepGroup> groups = plan_sweep(idx, closest, mem_freq, cap);
+    *count = (int32_t)groups.size();
+    for (int i = 0; i < n && i < (int)groups.size(); ++i) {
+        const SweepGroup &g = groups[i];
+        const int32_t v[4] = {g.first, g.t_lo, g.G, g.inserts ? 1 : 0};
+        for (int j = 0; j < 4; ++j) out[4 * i + j] = v[j];
+    }
+    return STCN_OK;
+}
+
 int stcn_memread_plan(int N, int Q, int32_t *plan7) {
     if (!plan7 || N < 1 || Q < 1) { set_error("stcn_memread_plan: bad arguments"); return STCN_E_INVALID; }
     const MemReadPlan pl = memread_plan(N, Q);

@@ -149,6 +149,11 @@ int stcn_test_conv_path(int B, int H, int W, int Cin, int Cout, int K, int strid
  * "wino2 ppw=1 splitk=2" (Winograd F(2x2,3x3)), "wino4 chunks=2 +tail" (F(4x4,3x3)), "fusion_wino", "fusion_direct", "n1".
  * Tests assert the path per shape: a silent fall-back to another instance would still pass a numerical comparison. */
 const char *stcn_last_conv_path(void);
+/* Test hook: the schedule of one sweep of an interaction, from the host-side planner alone (no GPU is needed).  The sweep visits the frames
+ * strictly between idx and closest, away from idx (closest < idx: backward), in decode groups of at most cap frames; mem_freq as given to
+ * stcn_engine_create.  Writes the first n groups in sweep order as 4 int32 each - { first frame in sweep order, lowest frame, frames,
+ * 1 if the group's last frame in sweep order is inserted into the memory bank } - and the number of groups of the sweep to *count. */
+int stcn_test_sweep_plan(int idx, int closest, int mem_freq, int cap, int32_t *out, int n, int32_t *count);
 /* Test hook: stcn_test_conv_trace(1) starts (and clears) a log of the CALLING THREAD's convolutions, one "layer=path\n" line per conv
  * enqueued (stage hooks and stcn_interact alike: engine launches happen on the caller's thread); (0) stops it; _get returns the log.
  * Lets a sequence test assert that e.g. every decoder layer of a 853x480 clip really ran as "wino4 ...". */
