@@ -52,6 +52,7 @@ PROTOTYPES = {
     "stcn_test_conv_trace_get": (C.c_char_p, []),
     "stcn_test_conv": (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 11),
     "stcn_test_conv_path": (_I, [_I] * 9 + [C.c_char_p, _I]),
+    "stcn_test_conv_plan": (_I, [_I] * 9 + [C.POINTER(C.c_int32), _I, C.POINTER(_D)]),
     "stcn_test_sweep_plan": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32)]),
     "stcn_test_encode_key": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "stcn_test_encode_value": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),

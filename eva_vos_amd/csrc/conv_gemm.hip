@@ -83,19 +83,15 @@ __global__ __launch_bounds__(256, (RM == 1 && RN == 1) ? STCN_PW_WAVES : 1) void
     float *Bs = smem + 2 * BM * LDT;   // [2][BN][LDT]
 
     // ---- block -> (split, m-tile, n-tile), XCD-contiguous (bijective remap)
-    auto xcd_contiguous = [](int bid, int nblk) {       // block id -> position in a per-XCD contiguous order
-        const int q8 = nblk >> 3, r8 = nblk & 7, xcd = bid & 7;
-        return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    };
     int split, tile, kper = kt_per_split;
     bool piece = false;                                // tail balancing: this workgroup computes a K piece of a tile
     if (p.rem_split > 1) {                             // blocks [0, rem_full): whole tiles; then the pieces
         const int bid = blockIdx.x;
         if (bid < p.rem_full) {
-            tile = xcd_contiguous(bid, p.rem_full);
+            tile = xcd_contiguous_block(bid, p.rem_full);
             split = 0;
         } else {
-            const int j = xcd_contiguous(bid - p.rem_full, (int)gridDim.x - p.rem_full);
+            const int j = xcd_contiguous_block(bid - p.rem_full, (int)gridDim.x - p.rem_full);
             const int rt = j / p.rem_split;
             split = j - rt * p.rem_split;
             tile = p.rem_full + rt;
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(256, (RM == 1 && RN == 1) ? STCN_PW_WAVES : 1) void
             piece = true;
         }
     } else {
-        const int swz = xcd_contiguous(blockIdx.x, gridDim.x);
+        const int swz = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x);
         split = fastdiv(swz, td.ntile);
         tile = swz - split * ntile;
     }
@@ -475,8 +471,7 @@ __global__ __launch_bounds__(256, STCN_PW_WAVES) void pw_chain_kernel(const Conv
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *As = smem;                  // [2][BM][LDT]
     float *Bs = smem + 2 * BM * LDT;   // [2][BN][LDT]
-    const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = blockIdx.x & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + ((int)blockIdx.x >> 3);      // XCD-contiguous
+    const int nb = gridDim.x, swz = xcd_contiguous_block((int)blockIdx.x, nb);
     // tile walk of this workgroup: tile0, tile0 + tstep, ... (< tile1).  Consecutive (p.kn.pw_chain == 1): nt neighbouring tiles - the
     // workgroup re-reads its own activation rows, which the residual / output streams of the 127 other workgroups of the XCD have
     // pushed out of the 4 MB L2 by then (FETCH_SIZE of the class +22 %).  Strided (default): in step j the grid as a whole covers the
@@ -639,8 +634,7 @@ static int pw_chain_tiles(const ConvP &p, int force_splitk) {
     // (a dropped store) while the output itself is shorter than 2 GiB - or when no such lane exists
     if ((p.N % 64) != 0 && ((long)p.M + 64) * p.N * 4 >= (1L << 31)) return 0;
     const long ntile = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-    static const int cus = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-    const long resident = (long)cus * STCN_PW_WAVES;                  // workgroups the chip holds at once (one wave per SIMD each)
+    const long resident = (long)device_cus() * STCN_PW_WAVES;         // workgroups the chip holds at once (one wave per SIMD each)
     if (ntile < resident + resident / 2) return 0;                    // up to 1.5 resident sets: the one-tile instance (with its tail balancing) is as good
     const long nt = (ntile + resident - 1) / resident;
     return (int)(nt > 16 ? 16 : nt);
@@ -721,7 +715,7 @@ static inline bool smallc_variant(const ConvP &p) {
 struct Plan { double cost; int big, splitk, rem_full, rem_split, rem_per; };
 
 static Plan plan_variant(const ConvP &p, bool big, int force_splitk, size_t ws_floats) {
-    static const bool tail_on = [] { const char *e = getenv("STCN_CONV_TAIL"); return !e || atoi(e) != 0; }();
+    static const bool tail_on = env_on("STCN_CONV_TAIL");
     const int BM = narrow_variant(p) ? 128 : (big ? 128 : 64), BN = narrow_variant(p) ? 32 : (big ? 128 : 64);
     const long tiles = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     const int nkt = p.Kp / BK;
@@ -767,7 +761,7 @@ static const char *conv_variant_name(const ConvP &p) {
 }
 
 void conv_plan(ConvP &p, int force_splitk, size_t ws_floats, ConvPlan &cp) {
-    static const int big_mode = [] { const char *e = getenv("STCN_CONV_BIG"); return e ? atoi(e) : 1; }();
+    static const int big_mode = env_int("STCN_CONV_BIG", 1);
     Plan pl = plan_variant(p, false, force_splitk, ws_floats);
     constexpr int big_mink = 2304;               // smallest padded K for the 128x128 instance (1x1 convs measured no gain from it)
     const bool big_ok = big_mode != 0 && !narrow_variant(p) && !smallc_variant(p) && p.N >= 128 && p.Kp >= big_mink;
@@ -789,6 +783,11 @@ void conv_plan(ConvP &p, int force_splitk, size_t ws_floats, ConvPlan &cp) {
     cp.splitk = p.splitk; cp.tail = p.rem_split > 1;
     cp.n_in = 0; cp.n_gemm = 1; cp.reduce = p.splitk > 1 || p.rem_split > 1;
     cp.fl_exec = cp.fl;
+}
+
+int device_cus() {
+    static const int cus = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
+    return cus;
 }
 
 // dynamic LDS above 64 KB has to be opted into once per (device, kernel function): a process may hold models on several

@@ -338,12 +338,7 @@ bool fusion_conv_plan(const ConvP &p, ConvPlan &pl) {
 void fusion_conv_launch(const ConvP &p, const ConvPlan &pl, hipStream_t s, hipEvent_t *ev) {
     constexpr int PH = 4;
     const int tiles_x = (p.W + 31) / 32, tiles_y = (p.H + PH - 1) / PH, n_patches = tiles_x * tiles_y;
-    static const int resident = [] {                  // two workgroups per CU (206 VGPRs: two waves per SIMD)
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        return 2 * (cus > 0 ? cus : 256);
-    }();
+    const int resident = 2 * device_cus();            // two workgroups per CU (206 VGPRs: two waves per SIMD)
     const dim3 grid((unsigned)(n_patches < resident ? n_patches : resident));
     if (pl.fusion_wino) {
         const size_t ldsw = (size_t)((PH + 2) * 34 * ((p.Cin + 7) / 8 * 8 + 4) + 4 * 2 * 32 * 32) * sizeof(float);

@@ -60,6 +60,27 @@ struct ConvRig {
         return STCN_OK;
     }
 };
+// The device-free set-up of stcn_test_conv's conv (stcn_test_conv_path / stcn_test_conv_plan): the same ConvW and Work sizes, planned but
+// neither allocated nor launched.  The planners test wino_u, wino4_u, partial, bias and res for null only, so one non-null constant
+// stands in for every buffer.  No residual.
+int plan_test_conv(int B, int H, int W, int Cin, int Cout, int K, int stride, int flags, int splitk, ConvP &p, ConvPlan &pl) {
+    static float buf[4];
+    Model m;
+    ConvW cw = test_convw(Cin, Cout, K, K);
+    cw.w = cw.bias = buf;
+    const int OH = (H + 2 * (K / 2) - K) / stride + 1, OW = (W + 2 * (K / 2) - K) / stride + 1;
+    Work w;
+    if (K == 3 && stride == 1) {
+        if (wants_wino(cw) || wants_wino_fusion12(cw)) cw.wino_u = buf;
+        if (flags & 4) { if (wants_wino4(cw)) cw.wino4_u = buf; m.wino4_min_wg = 0; }
+        w.wino_v_floats = test_wino_v_floats(B, OH, OW, Cin);
+        w.wino_v = buf;
+    }
+    m.conv["t"] = cw;
+    w.splitk_floats = (size_t)16 * 1024 * 1024;
+    w.splitk = buf;
+    return plan_conv(m, w, "t", ConvArgs(buf, Cin, B, H, W).strided(stride).out(buf).relu(flags & 1, (flags >> 1) & 1).splitk(splitk), p, pl);
+}
 }  // namespace
 
 extern "C" {
@@ -100,29 +121,33 @@ int stcn_test_conv(void *stream, const float *x, const float *wgt, const float *
 }
 
 // The plan stcn_test_conv's conv would take, as its path string: the same ConvW and Work sizes, but nothing is allocated on a device
-// and nothing is launched (works without a GPU).  The planners test wino_u, wino4_u, partial, bias and res for null only, so one
-// non-null constant stands in for every buffer.  No residual.
+// and nothing is launched (works without a GPU).
 int stcn_test_conv_path(int B, int H, int W, int Cin, int Cout, int K, int stride, int flags, int splitk, char *out, int n) {
     if (Cin % 4 || !out || n < 1) { set_error("stcn_test_conv_path: Cin%%4==0 and an output buffer required"); return STCN_E_INVALID; }
-    static float buf[4];
-    Model m;
-    ConvW cw = test_convw(Cin, Cout, K, K);
-    cw.w = cw.bias = buf;
-    const int OH = (H + 2 * (K / 2) - K) / stride + 1, OW = (W + 2 * (K / 2) - K) / stride + 1;
-    Work w;
-    if (K == 3 && stride == 1) {
-        if (wants_wino(cw) || wants_wino_fusion12(cw)) cw.wino_u = buf;
-        if (flags & 4) { if (wants_wino4(cw)) cw.wino4_u = buf; m.wino4_min_wg = 0; }
-        w.wino_v_floats = test_wino_v_floats(B, OH, OW, Cin);
-        w.wino_v = buf;
-    }
-    m.conv["t"] = cw;
-    w.splitk_floats = (size_t)16 * 1024 * 1024;
-    w.splitk = buf;
     ConvP p;
     ConvPlan pl;
-    RC(plan_conv(m, w, "t", ConvArgs(buf, Cin, B, H, W).strided(stride).out(buf).relu(flags & 1, (flags >> 1) & 1).splitk(splitk), p, pl));
+    RC(plan_test_conv(B, H, W, Cin, Cout, K, stride, flags, splitk, p, pl));
     format_conv_path(pl, out, (size_t)n);
+    return STCN_OK;
+}
+
+// ... and the same plan in numbers (the path string leaves most of it out); the order is the one include/stcn_hip.h documents.
+// Fields of other families than the plan's are zero.
+int stcn_test_conv_plan(int B, int H, int W, int Cin, int Cout, int K, int stride, int flags, int splitk, int32_t *iv, int n, double *dv) {
+    if (Cin % 4 || !iv || n < STCN_CONV_PLAN_INTS || !dv) { set_error("stcn_test_conv_plan: Cin%%4==0, STCN_CONV_PLAN_INTS ints and 2 doubles required"); return STCN_E_INVALID; }
+    ConvP p;
+    ConvPlan pl;
+    RC(plan_test_conv(B, H, W, Cin, Cout, K, stride, flags, splitk, p, pl));
+    const bool w2 = pl.family == CONV_WINO2, w4 = pl.family == CONV_WINO4, direct = pl.family == CONV_DIRECT;
+    const WinoGeom g = w2 || w4 ? pl.geo : WinoGeom{};
+    const W4Plan q = w4 ? pl.w4 : W4Plan{};
+    const int32_t v[STCN_CONV_PLAN_INTS] = {
+        pl.family, pl.splitk, pl.ppw, pl.tail, pl.n_in, pl.n_gemm, pl.reduce,
+        g.TH, g.TW, g.Mt, g.Mt_pad, g.KB, w2 ? pl.w2.kb_per_split : 0,
+        q.mb, q.tiles_m, q.tiles_n, q.grid, q.full_wg, q.pieces, q.per, q.chunks, q.tm_per_chunk,
+        direct ? p.tile_big : 0, direct ? p.rem_full : 0, direct ? p.rem_split : 0, direct ? p.rem_per : 0, direct ? p.chain : 0};
+    for (int i = 0; i < STCN_CONV_PLAN_INTS; ++i) iv[i] = v[i];
+    dv[0] = (double)pl.v_floats; dv[1] = pl.fl_exec;
     return STCN_OK;
 }
 
@@ -369,9 +394,7 @@ int stcn_metrics_round(void *stream, const uint8_t *masks_dev, int nh, int nw, i
 int stcn_bench_mfma_rate(void *stream, int ms_target, float *tflops, float *ms_out) {
     if (!tflops || ms_target < 1 || ms_target > 2000) { set_error("stcn_bench_mfma_rate: bad arguments"); return STCN_E_INVALID; }
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0, cus = 256;
-    HIPCHK(hipGetDevice(&dev));
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = device_cus();
     DevBuf out;
     RC(out.alloc(64));
     hipEvent_t e0, e1;

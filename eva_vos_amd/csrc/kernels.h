@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+
 #include "../../include/stcn_hip.h"   // STCN_MAX_OBJECTS
 
 namespace stcn {
@@ -36,6 +38,14 @@ __device__ __forceinline__ int xcd_contiguous_block(int bid, int nblk) {
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 #endif
+
+// ---------------------------------------------------------------- process-level switches and the device's size
+// A switch that holds for the whole process is a function-local `static const` initialised from one of these, so the variable is read
+// once, at the first use (not per workspace as the Knobs below: moving one there would change when it takes effect).
+static inline int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+static inline bool env_on(const char *name, bool dflt = true) { return env_int(name, dflt) != 0; }
+// compute units of the current device at the first call (256 when it cannot be asked); read once per process
+int device_cus();
 
 // ---------------------------------------------------------------- launch-level tunables
 // Read from the environment ONCE per workspace (= once per engine, once per stage-hook call) by Knobs::from_env() and carried in
@@ -94,13 +104,21 @@ struct ConvP {
 // Filled ONCE per run_conv call (engine.cpp plan_conv) by the planning function of the family that takes the conv; the accounting, the
 // profiling event pairs, the path string of the tests and the family's launch function all read this one object - nothing plans again.
 constexpr int W4_MAX_CHUNKS = 16;       // most slices of a chunked F(4x4) launch (wino4_plan); one profiling event pair per slice
-// launch plan of the F(4x4) GEMM: 64- or 32-tile workgroups, and (32-tile only) the tail split
-struct W4Plan { int Mt, Mt_pad, tiles_m, tiles_n, mb, grid, full_wg, pieces, per, chunks, tm_per_chunk; };
+// tile geometry of a Winograd conv (wino_geom): TH x TW output tiles per image, Mt of them in the batch, padded to whole workgroup tiles;
+// KB k-blocks of 8 input channels
+struct WinoGeom { int TH, TW, Mt, Mt_pad, KB; };
+// launch plan of the F(2x2) GEMM: ntile = (Mt_pad / 64) x tiles_n workgroup tiles, each cut into ConvPlan::splitk ranges of kb_per_split k-blocks
+struct W2Plan { int tiles_n, ntile, kb_per_split; };
+// launch plan of the F(4x4) GEMM: 64- or 32-tile workgroups, and (32-tile only) the tail split.  judge_wg: the workgroup count that
+// eligibility holds against Model::wino4_min_wg (wino4_gemm_plan says how it differs from grid)
+struct W4Plan { int tiles_m, tiles_n, mb, grid, full_wg, pieces, per, chunks, tm_per_chunk, judge_wg; };
 enum ConvFamily { CONV_LITERAL = 0, CONV_FUSION = 1, CONV_WINO4 = 2, CONV_WINO2 = 3, CONV_DIRECT = 4 };
 struct ConvPlan {
     int family = CONV_LITERAL;
     bool fusion_wino = false;       // CONV_FUSION: Winograd F(2x2,3x3) inside the workgroup (else the direct FusionNet kernel)
+    WinoGeom geo{};                 // CONV_WINO4, CONV_WINO2
     W4Plan w4{};                    // CONV_WINO4
+    W2Plan w2{};                    // CONV_WINO2
     int splitk = 1;                 // CONV_WINO2: split-K of the Winograd GEMM; CONV_DIRECT: p.splitk
     int ppw = 0;                    // CONV_WINO2: GEMM instance (positions per wave)
     const char *variant = "";       // CONV_DIRECT: conv_variant_name() (the tile plan itself is in ConvP: the kernels read it)

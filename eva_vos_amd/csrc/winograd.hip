@@ -21,11 +21,12 @@
 //     of conv_reduce_kernel (the output transform is linear).
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
-#include "kernels.h"
+#include "wino_common.h"
 
 namespace stcn {
 
@@ -45,9 +46,7 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float *__restrict
                                                          int TH, int TW, int Mt, int Mt_pad, int cb_per_chunk,
                                                          float *__restrict__ V) {
     // XCD-contiguous block order (neighbouring tile rows share pixel rows: keep them in one L2)
-    const int nbx = gridDim.x, q8 = nbx >> 3, r8 = nbx & 7, xcd = blockIdx.x & 7;
-    const int bx = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    const long i = bx * 256L + threadIdx.x;
+    const long i = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x) * 256L + threadIdx.x;
     const int c16 = (int)(i & 7);
     const long tile = i >> 3;
     if (tile >= Mt_pad) return;
@@ -123,12 +122,7 @@ template <int PPW>
 __global__ __launch_bounds__(1024 / PPW) void wino_gemm_kernel(const WinoG p, const int tiles_n, const int ntile) {
     constexpr int NT = 1024 / PPW;                                          // threads per workgroup
     extern __shared__ __attribute__((aligned(16))) float smem[];          // epilogue: [16][64][32]
-    const int nblk = gridDim.x;
-    auto xcd_contiguous = [](int bid, int nb) {
-        const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-        return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    };
-    const int swz = xcd_contiguous(blockIdx.x, nblk);
+    const int swz = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x);
     const int split = fastdiv(swz, p.fd_ntile), tile = swz - split * ntile;
     const int tm = fastdiv(tile, p.fd_tiles_n), tn = tile - tm * tiles_n;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, h = lane >> 5;
@@ -215,7 +209,7 @@ __global__ __launch_bounds__(1024 / PPW) void wino_gemm_kernel(const WinoG p, co
     const int chq = t & 7, tl = (t >> 3) & 63;
     const int tpi = p.TH * p.TW, ohw = p.OH * p.OW;
     const bool part = p.splitk > 1;
-    // residual / output through buffer resources: 32-bit byte offsets (extents < 4 GiB: wino_workspace_floats); a masked store
+    // residual / output through buffer resources: 32-bit byte offsets (extents < 4 GiB: wino_extents_ok); a masked store
     // is an out-of-range offset
     const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.res ? p.res : p.y), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(part ? p.partial : p.y, 0, -1, 0x00020000);
@@ -296,50 +290,34 @@ __global__ __launch_bounds__(1024 / PPW) void wino_gemm_kernel(const WinoG p, co
 
 // ------------------------------------------------------------------------------------------------ host side
 bool wino_enabled() {
-    static const bool on = [] { const char *e = getenv("STCN_WINOGRAD"); return !e || atoi(e) != 0; }();
+    static const bool on = env_on("STCN_WINOGRAD");
     return on;
 }
 
-// floats of V workspace the Winograd path needs for this conv (0: not eligible)
-static size_t wino_workspace_floats(const ConvP &p) {
-    if (!wino_enabled() || !p.wino_u || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.x1) return 0;
-    if (p.Cin % 32 || p.Cin < p.kn.wino_min_cin || p.N % WN || p.bs0 == 0) return 0;
-    const long Mt = (long)p.B * ((p.OH + 1) / 2) * ((p.OW + 1) / 2);
-    const long Mt_pad = (Mt + WT - 1) / WT * WT;
+// Takes the conv when the shape is eligible and V fits; then the whole launch is planned here: geometry, split-K, GEMM instance.
+bool wino_plan(const ConvP &p, size_t v_cap, size_t slab_floats, ConvPlan &pl) {
+    if (!wino_enabled() || !p.wino_u || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.x1) return false;
+    if (p.Cin % 32 || p.Cin < p.kn.wino_min_cin || p.N % WN || p.bs0 == 0) return false;
+    const WinoGeom ge = wino_geom(p, 2, WT);
     // 64-channel layers (K = 8 k-blocks; opt-in: STCN_WINO_MIN_CIN=64): the transforms and the epilogue outweigh the MFMA saving
     // unless the launch is large - 64 -> 64 at 120x216 over a 5-frame group (32400 tiles): 94 -> 76 us back to back, but 81 -> 78 us
     // inside the engine's launch sequence (rocprofv3 trace): not worth 133 MB of V per layer; one frame (6480 tiles): 26 -> 32 us
-    if (p.Cin < 128 && Mt < 16384) return 0;
-    if (16L * p.Cin * Mt_pad * 4 >= (1L << 32)) return 0;                  // 32-bit buffer offsets
-    if ((long)p.B * (p.y_bs ? p.y_bs : (long)p.OH * p.OW * p.N) * 4 >= (1L << 32)) return 0;
-    if (p.res && (long)(p.res_bmod ? p.res_bmod : p.B) * p.res_bs * 4 >= (1L << 32)) return 0;
-    return (size_t)16 * p.Cin * Mt_pad;
-}
-
-// split-K of the Winograd GEMM: with few (tile, channel) workgroups the input channels are cut so that about one round of
-// CUs is busy; the pieces write transformed partial sums into the slabs of conv_reduce_kernel
-static int wino_splitk(const ConvP &p, size_t slab_floats) {
-    const int TH = (p.OH + 1) / 2, TW = (p.OW + 1) / 2;
-    const int Mt_pad = (p.B * TH * TW + WT - 1) / WT * WT, KB = p.Cin / 8;
-    const int ntile = (Mt_pad / WT) * (p.N / WN);
-    constexpr int split_below = 160;             // (64 / 128 / 160 measured in round 3: +1.3 / +1.3 / 0 % kernel time)
-    int sk = 1;
-    if (ntile < split_below) {
-        sk = (256 + ntile - 1) / ntile;
-        const int smax = KB / 8 < 1 ? 1 : KB / 8;        // at least 8 k-blocks per piece
-        sk = sk > smax ? smax : sk;
-        while (sk > 1 && (size_t)sk * p.M * p.N > slab_floats) --sk;
-    }
-    const int per = (KB + sk - 1) / sk;
-    return (KB + per - 1) / per;
-}
-
-bool wino_plan(const ConvP &p, size_t v_cap, size_t slab_floats, ConvPlan &pl) {
-    const size_t need = wino_workspace_floats(p);
-    if (need == 0 || need > v_cap) return false;
+    if (p.Cin < 128 && ge.Mt < 16384) return false;
+    if (!wino_extents_ok(p, 16, ge.Mt_pad)) return false;
+    const size_t need = (size_t)16 * p.Cin * ge.Mt_pad;
+    if (need > v_cap) return false;
     pl.family = CONV_WINO2;
+    pl.geo = ge;
     pl.v_floats = need;
-    pl.splitk = wino_splitk(p, slab_floats);
+    // split-K of the GEMM: with few (tile, channel) workgroups the input channels are cut (at least 8 k-blocks per piece, as many slabs
+    // as p.partial holds) so that about one round of CUs is busy; the pieces write transformed partial sums into the slabs of
+    // conv_reduce_kernel
+    pl.w2.tiles_n = p.N / WN;
+    pl.w2.ntile = (ge.Mt_pad / WT) * pl.w2.tiles_n;
+    constexpr int split_below = 160;             // (64 / 128 / 160 measured in round 3: +1.3 / +1.3 / 0 % kernel time)
+    const int slabs = (int)std::max<size_t>(1, std::min<size_t>(256, slab_floats / ((size_t)p.M * p.N)));
+    const KPieces kp = pl.w2.ntile < split_below ? k_pieces((256 + pl.w2.ntile - 1) / pl.w2.ntile, ge.KB, 8, slabs) : KPieces{1, ge.KB};
+    pl.splitk = kp.pieces; pl.w2.kb_per_split = kp.per;
     // 16 waves x 1 position (4 waves per SIMD) feed the matrix pipe a little better on the short-K layers (+1.5-3 % up to 512
     // input channels); with 1024+ channels the 8-wave form with its deeper per-wave prefetch is as good or better
     const int ppw_env = p.kn.wino_ppw;                    // tests run every shape under both instances
@@ -352,59 +330,29 @@ bool wino_plan(const ConvP &p, size_t v_cap, size_t slab_floats, ConvPlan &pl) {
 // Winograd launch of a conv that wino_plan() accepted; V >= pl.v_floats floats.  ev: optional {start, stop} pairs for
 // the transform, GEMM and reduce dispatches.
 void wino_launch(const ConvP &p, const ConvPlan &pl, float *V, hipStream_t s, hipEvent_t *ev_in, hipEvent_t *ev_gemm, hipEvent_t *ev_red) {
-    const int TH = (p.OH + 1) / 2, TW = (p.OW + 1) / 2;
-    const int Mt = p.B * TH * TW, Mt_pad = (Mt + WT - 1) / WT * WT, KB = p.Cin / 8;
-    // ---- input transform: 8 threads per tile, the 32-channel blocks cut into chunks so that the grid fills the chip
-    {
-        const unsigned gx = (unsigned)((8L * Mt_pad + 255) / 256);
-        const int NCB = p.Cin / 32;
-        int chunks = (int)((2048 + gx - 1) / gx);
-        chunks = chunks < 1 ? 1 : (chunks > NCB ? NCB : chunks);
-        const int per = (NCB + chunks - 1) / chunks;
-        chunks = (NCB + per - 1) / per;
-        launch(wino_input_kernel, dim3(gx, chunks), dim3(256), 0, s, ev_in, p.x0, p.bs0, p.H, p.W, p.Cin, p.relu_in, TH, TW, Mt, Mt_pad, per, V);
-    }
-    // ---- GEMM
+    const WinoGeom &ge = pl.geo;
+    const WinoInGrid ig = wino_input_grid(ge.Mt_pad, p.Cin);
+    launch(wino_input_kernel, dim3(ig.gx, ig.chunks), dim3(256), 0, s, ev_in, p.x0, p.bs0, p.H, p.W, p.Cin, p.relu_in, ge.TH, ge.TW, ge.Mt, ge.Mt_pad,
+           ig.per, V);
     WinoG g{};
-    g.V = V; g.U = p.wino_u;
-    g.v_bytes = (unsigned)((size_t)16 * p.Cin * Mt_pad * 4);
-    g.u_bytes = (unsigned)((size_t)16 * p.Cin * p.N * 4);
-    g.Mt = Mt; g.Mt_pad = Mt_pad; g.KB = KB; g.N = p.N;
-    g.TH = TH; g.TW = TW; g.OH = p.OH; g.OW = p.OW; g.B = p.B; g.M = p.M;
-    g.bias = p.bias; g.res = p.res; g.res_bs = p.res_bs; g.res_bmod = p.res_bmod; g.y = p.y; g.y_bs = p.y_bs; g.relu_out = p.relu_out;
-    const int tiles_m = Mt_pad / WT, tiles_n = p.N / WN, ntile = tiles_m * tiles_n;
-    g.fd_tpi = fastdiv_make((unsigned)(TH * TW)); g.fd_tw = fastdiv_make((unsigned)TW);
-    g.fd_ntile = fastdiv_make((unsigned)ntile); g.fd_tiles_n = fastdiv_make((unsigned)tiles_n);
-    const int sk = pl.splitk;
-    g.kb_per_split = (KB + sk - 1) / sk;
-    g.splitk = sk; g.partial = p.partial;
+    wino_fill_desc(g, p, ge, 16, V, p.wino_u, pl.w2.tiles_n);
+    g.fd_ntile = fastdiv_make((unsigned)pl.w2.ntile);
+    g.splitk = pl.splitk; g.kb_per_split = pl.w2.kb_per_split; g.partial = p.partial;
     const size_t lds = (size_t)16 * WT * 32 * sizeof(float);
-    if (pl.ppw == 1) launch(wino_gemm_kernel<1>, dim3(ntile * sk), dim3(1024), lds, s, ev_gemm, g, tiles_n, ntile);
-    else launch(wino_gemm_kernel<2>, dim3(ntile * sk), dim3(512), lds, s, ev_gemm, g, tiles_n, ntile);
-    if (sk > 1) {
+    const dim3 grid(pl.w2.ntile * pl.splitk);
+    if (pl.ppw == 1) launch(wino_gemm_kernel<1>, grid, dim3(1024), lds, s, ev_gemm, g, pl.w2.tiles_n, pl.w2.ntile);
+    else launch(wino_gemm_kernel<2>, grid, dim3(512), lds, s, ev_gemm, g, pl.w2.tiles_n, pl.w2.ntile);
+    if (pl.splitk > 1) {
         ConvP q = p;
-        q.splitk = sk;
+        q.splitk = pl.splitk;
         conv_reduce_launch(q, s, ev_red);
     }
 }
 
-// U [16][Cin/8][N][8] from the BN-folded direct weights w [N][Kp] (k = (ky*3 + kx) * Cin + c), on the host in double
+// U [16][Cin/8][N][8]
 void wino_transform_weights(const float *w, int N, int Cin, int Kp, float *U) {
     static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    const int KB = Cin / 8;
-    for (int n = 0; n < N; ++n)
-        for (int c = 0; c < Cin; ++c) {
-            double g[3][3], tmp[4][3];
-            for (int ky = 0; ky < 3; ++ky)
-                for (int kx = 0; kx < 3; ++kx) g[ky][kx] = w[(size_t)n * Kp + (size_t)(ky * 3 + kx) * Cin + c];
-            for (int i = 0; i < 4; ++i)
-                for (int kx = 0; kx < 3; ++kx) tmp[i][kx] = G[i][0] * g[0][kx] + G[i][1] * g[1][kx] + G[i][2] * g[2][kx];
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j) {
-                    const double u = tmp[i][0] * G[j][0] + tmp[i][1] * G[j][1] + tmp[i][2] * G[j][2];
-                    U[((((size_t)(i * 4 + j) * KB + c / 8) * N + n) << 3) + (c & 7)] = (float)u;
-                }
-        }
+    wino_transform_weights_with(G, w, N, Cin, Kp, U);
 }
 
 }  // namespace stcn

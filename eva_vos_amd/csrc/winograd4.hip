@@ -28,7 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "kernels.h"
+#include "wino_common.h"
 
 namespace stcn {
 
@@ -83,9 +83,7 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float *__restric
                                                           int tile_lo, int tile_hi, float *__restrict__ V) {
     // XCD-contiguous block order: neighbouring tile rows share two pixel rows; dealt round-robin over the XCDs (the dispatcher's
     // order) those rows were fetched into two L2s - FETCH_SIZE 2.1x the input
-    const int nbx = gridDim.x, q8 = nbx >> 3, r8 = nbx & 7, xcd = blockIdx.x & 7;
-    const int bx = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (blockIdx.x >> 3);
-    const long i = bx * 256L + threadIdx.x;
+    const long i = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x) * 256L + threadIdx.x;
     const int c16 = (int)(i & 7);
     const long tile = tile_lo + (i >> 3);                    // [tile_lo, tile_hi): the launch's slice of the tiles (whole V when not chunked)
     if (tile >= tile_hi) return;
@@ -167,20 +165,16 @@ template <int MB>
 __global__ __launch_bounds__(64 * W4W) void wino4_gemm_kernel(const Wino4G p, const int tiles_n) {
     constexpr int PPW = 3, WT = W4T * MB;
     extern __shared__ __attribute__((aligned(16))) float smem[];          // epilogue: [36][32 tiles][32 channels]
-    auto xcd_contiguous = [](int bid, int nb) {
-        const int q8 = nb >> 3, r8 = nb & 7, xcd = bid & 7;
-        return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    };
     int swz, piece = -1, kb0 = 0, kb1 = p.KB;
     if (MB == 1 && p.pieces > 1 && (int)blockIdx.x >= p.full_wg) {           // a K piece of one of the last tiles
-        const int j = xcd_contiguous((int)blockIdx.x - p.full_wg, (int)gridDim.x - p.full_wg);
+        const int j = xcd_contiguous_block((int)blockIdx.x - p.full_wg, (int)gridDim.x - p.full_wg);
         const int rt = j / p.pieces;
         piece = j - rt * p.pieces;
         swz = p.full_wg + rt;
         kb0 = piece * p.kb_per_piece;
         kb1 = min(p.KB, kb0 + p.kb_per_piece);
     } else {
-        swz = xcd_contiguous(blockIdx.x, MB == 1 && p.pieces > 1 ? p.full_wg : (int)gridDim.x);
+        swz = xcd_contiguous_block((int)blockIdx.x, MB == 1 && p.pieces > 1 ? p.full_wg : (int)gridDim.x);
     }
     int tm_l = fastdiv(swz, p.fd_tiles_n), tn = swz - tm_l * tiles_n;
     if (p.xb_m > 0 && piece < 0) {                                            // swz = block * (xb_m xb_n) + row-major position inside the block
@@ -336,7 +330,7 @@ __global__ __launch_bounds__(64 * W4W) void wino4_gemm_kernel(const Wino4G p, co
     const int n = tn * W4N + 4 * chq;
     const bool kpiece = MB == 1 && piece >= 0;
     const float lo = p.relu_out ? 0.f : -__builtin_inff();
-    // residual / output through buffer resources: 32-bit byte offsets (extents < 4 GiB: wino4_workspace_floats), a masked store is
+    // residual / output through buffer resources: 32-bit byte offsets (extents < 4 GiB: wino_extents_ok), a masked store is
     // an out-of-range offset
     const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.res ? p.res : p.y), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, -1, 0x00020000);
@@ -485,87 +479,59 @@ __global__ __launch_bounds__(256) void wino4_reduce_kernel(const Wino4G p, const
 
 // ------------------------------------------------------------------------------------------------ host side
 int wino4_mode() {                 // 0 off, 1 on for flagged layers with enough workgroups (default), 2 whenever the shape allows
-    static const int m = [] { const char *e = getenv("STCN_WINO4"); return e ? atoi(e) : 1; }();
+    static const int m = env_int("STCN_WINO4", 1);
     return m;
-}
-
-static int wino4_cus() {
-    static const int cus = [] { int dev = 0, n = 256; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-    return cus;
 }
 
 // Small launches (round 4): a layer whose 32-tile workgroups do not even fill HALF a round of CUs - the value encoder's fuser and
 // its frame parts at batch 1 (1620 pixels x 512 channels = 64 workgroups), the 1/16-scale decoder layers of a single frame - used
-// to fall back to F(2x2) with split-K (threshold STCN_WINO4_MIN_WG).  The K pieces of the tail split generalise: EVERY tile is cut
-// into up to 8 pieces of >= 8 k-blocks so that about one round of CUs is busy, the output-domain partial sums meet in
-// wino4_reduce_kernel.  Returns the pieces per tile (1: leave the launch alone).
-static int wino4_small_pieces(int grid, int KB) {
-    static const bool on = [] { const char *e = getenv("STCN_WINO4_SMALL"); return !e || atoi(e) != 0; }();
-    const int cus = wino4_cus();
-    if (!on || grid * 2 > cus) return 1;
-    constexpr int min_kb = 8;                                    // k-blocks per piece, at least (4 / 8 / 16 measured equal on the solo leg, round 4)
-    int sp = cus / grid;
-    sp = sp > 8 ? 8 : sp;
-    while (sp > 1 && KB / sp < min_kb) --sp;
-    const int per = (KB + sp - 1) / sp;
-    return (KB + per - 1) / per;
-}
-
-// floats of V workspace the F(4x4) path needs for this conv (0: not eligible).  min_wg: fewest workgroups worth launching
-static size_t wino4_workspace_floats(const ConvP &p, int min_wg) {
-    if (!wino4_mode() || !p.wino4_u || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.x1) return 0;
-    if (p.Cin % 32 || p.Cin < W4_MIN_CIN || p.N % W4N || p.bs0 == 0) return 0;
-    const long Mt = (long)p.B * ((p.OH + 3) / 4) * ((p.OW + 3) / 4);
-    const long Mt_pad = (Mt + 2 * W4T - 1) / (2 * W4T) * (2 * W4T);          // whole 64-tile workgroup tiles
-    if (36L * p.Cin * Mt_pad * 4 >= (1L << 32)) return 0;                   // 32-bit buffer offsets
-    if ((long)p.B * (p.y_bs ? p.y_bs : (long)p.OH * p.OW * p.N) * 4 >= (1L << 32)) return 0;
-    if (p.res && (long)(p.res_bmod ? p.res_bmod : p.B) * p.res_bs * 4 >= (1L << 32)) return 0;
-    long wgs = (Mt_pad / W4T) * (p.N / W4N);
-    if (wgs * 2 <= wino4_cus()) wgs *= wino4_small_pieces((int)wgs, p.Cin / 8);   // a small launch is cut into K pieces (wino4_plan)
-    if (wino4_mode() < 2 && wgs < min_wg) return 0;                          // still too few workgroups: F(2x2) with its split-K is better
-    return (size_t)36 * p.Cin * Mt_pad;
+// to fall back to F(2x2) with split-K (threshold Model::wino4_min_wg).  The K pieces of the tail split generalise: EVERY tile is cut
+// into up to 8 pieces of >= 8 k-blocks (4 / 8 / 16 measured equal on the solo leg, round 4) so that about one round of CUs is busy, the
+// output-domain partial sums meet in wino4_reduce_kernel.  Returns the pieces per tile (1: leave the launch alone).
+static KPieces wino4_small_pieces(int grid, int KB) {
+    static const bool on = env_on("STCN_WINO4_SMALL");
+    const int cus = device_cus();
+    if (!on || grid * 2 > cus) return {1, KB};
+    return k_pieces(cus / grid, KB, 8, 8);
 }
 
 // launch plan of the F(4x4) GEMM: 64- or 32-tile workgroups, and (32-tile only) the tail split
-static W4Plan wino4_gemm_plan(const ConvP &p, size_t slab_floats) {
-    static const int mb_env = [] { const char *e = getenv("STCN_WINO4_MB"); return e ? atoi(e) : 0; }();
-    static const bool tail_on = [] { const char *e = getenv("STCN_WINO4_TAIL"); return !e || atoi(e) != 0; }();
-    const int cus = wino4_cus();
+static W4Plan wino4_gemm_plan(const ConvP &p, const WinoGeom &ge, size_t slab_floats) {
+    static const int mb_env = env_int("STCN_WINO4_MB", 0);
+    static const bool tail_on = env_on("STCN_WINO4_TAIL");
+    const int cus = device_cus(), KB = ge.KB;
     W4Plan pl{};
-    const int TH = (p.OH + 3) / 4, TW = (p.OW + 3) / 4, KB = p.Cin / 8;
-    pl.Mt = p.B * TH * TW;
-    pl.Mt_pad = (pl.Mt + 2 * W4T - 1) / (2 * W4T) * (2 * W4T);
     pl.tiles_n = p.N / W4N;
     // 64-tile workgroups (25 % fewer L2 bytes per MFMA: +6 % at 1/4 and 1/8 scale) unless they would leave CUs idle
-    pl.mb = mb_env == 1 || mb_env == 2 ? mb_env : ((pl.Mt_pad / (2 * W4T)) * pl.tiles_n >= 200 ? 2 : 1);
-    pl.tiles_m = pl.Mt_pad / (W4T * pl.mb);
+    pl.mb = mb_env == 1 || mb_env == 2 ? mb_env : ((ge.Mt_pad / (2 * W4T)) * pl.tiles_n >= 200 ? 2 : 1);
+    pl.tiles_m = ge.Mt_pad / (W4T * pl.mb);
     pl.grid = pl.tiles_m * pl.tiles_n;
     pl.full_wg = pl.grid; pl.pieces = 1; pl.per = KB;
+    const bool may_split = tail_on && pl.mb == 1 && p.partial;               // K pieces exist in the 32-tile form only and need the slabs
     // Tail split (32-tile workgroups): one workgroup per CU is resident (144 KB of LDS), so a grid of 288 workgroups - the
     // 1/16-scale 512-channel layers over a 5-frame group - costs two rounds for 1.125 rounds of work.  The whole rounds run as they
     // are; the tiles of the ragged last round are cut into K pieces that fill the chip once more (32 tiles x 8 pieces of 8 k-blocks:
     // 1.125 instead of 2 tile times) and meet in wino4_reduce_kernel.
-    if (tail_on && pl.mb == 1 && p.partial) {
+    if (may_split) {
         const int full = pl.grid / cus * cus, rem = pl.grid - full;
         if (full >= cus && rem > 0 && rem <= cus / 2) {
-            int sp = cus / rem;
-            sp = sp > 8 ? 8 : sp;
-            while (sp > 1 && KB / sp < 8) --sp;                               // at least 8 k-blocks per piece
-            const int per = (KB + sp - 1) / sp;
-            sp = (KB + per - 1) / per;
-            if (sp > 1 && (size_t)rem * sp * W4T * 16 * W4N <= slab_floats) {
-                pl.full_wg = full; pl.pieces = sp; pl.per = per;
-                pl.grid = full + rem * sp;
+            const KPieces kp = k_pieces(cus / rem, KB, 8, 8);
+            if (kp.pieces > 1 && (size_t)rem * kp.pieces * W4T * 16 * W4N <= slab_floats) {
+                pl.full_wg = full; pl.pieces = kp.pieces; pl.per = kp.per;
+                pl.grid = full + rem * kp.pieces;
             }
         }
     }
-    // Small launches: every tile in K pieces (see wino4_small_pieces)
-    if (tail_on && pl.mb == 1 && p.partial && pl.pieces == 1 && pl.grid * 2 <= cus) {
-        const int sp = wino4_small_pieces(pl.grid, KB);
-        if (sp > 1 && (size_t)pl.grid * sp * W4T * 16 * W4N <= slab_floats) {
-            pl.full_wg = 0; pl.pieces = sp; pl.per = (KB + sp - 1) / sp;
-            pl.grid *= sp;
-        }
+    // Small launches: every tile in K pieces (see wino4_small_pieces).
+    // What eligibility counts (judge_wg) is NOT what is launched (grid): it is the 32-tile workgroups times the small-launch pieces
+    // whatever may_split and the slab capacity say - under STCN_WINO4_TAIL=0, STCN_WINO4_MB=2, without slabs or with too few of them the
+    // pieces are counted and then not cut.  Kept as it has always decided; to be settled on its own.
+    const int wg32 = (ge.Mt_pad / W4T) * pl.tiles_n;
+    const KPieces small = wino4_small_pieces(wg32, KB);
+    pl.judge_wg = wg32 * small.pieces;
+    if (may_split && pl.pieces == 1 && small.pieces > 1 && (size_t)pl.grid * small.pieces * W4T * 16 * W4N <= slab_floats) {
+        pl.full_wg = 0; pl.pieces = small.pieces; pl.per = small.per;
+        pl.grid *= small.pieces;
     }
     // Chunked launches (64-tile workgroups): V of the 1/4-scale decoder layers over a 5-frame group is 299 MB - written by the
     // transform, it has left the 256 MB memory-side cache before the GEMM reads it, and the GEMM's loads (one half-step ahead)
@@ -573,7 +539,7 @@ static W4Plan wino4_gemm_plan(const ConvP &p, size_t slab_floats) {
     // and GEMM alternate over slices of whole rounds whose V stays under ~160 MB.
     pl.chunks = 1; pl.tm_per_chunk = pl.tiles_m;
     const long chunk_bytes = (long)p.kn.wino4_chunk_mb << 20;                  // tests run shapes under tiny chunks
-    const long vbytes = 36L * p.Cin * pl.Mt_pad * 4;
+    const long vbytes = 36L * p.Cin * ge.Mt_pad * 4;
     if (pl.mb == 2 && chunk_bytes > 0 && vbytes > chunk_bytes * 3 / 2) {
         const int rounds = (pl.grid + cus - 1) / cus;
         const int n = (int)((vbytes + chunk_bytes - 1) / chunk_bytes);
@@ -584,13 +550,21 @@ static W4Plan wino4_gemm_plan(const ConvP &p, size_t slab_floats) {
     }
     return pl;
 }
+
+// min_wg: fewest workgroups worth launching.  The launch is planned first and judged from that plan; cp is written on acceptance only.
 bool wino4_plan(const ConvP &p, int min_wg, size_t v_cap, size_t slab_floats, ConvPlan &cp) {
-    const size_t need = wino4_workspace_floats(p, min_wg);
-    if (need == 0 || need > v_cap) return false;
+    if (!wino4_mode() || !p.wino4_u || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.x1) return false;
+    if (p.Cin % 32 || p.Cin < W4_MIN_CIN || p.N % W4N || p.bs0 == 0) return false;
+    const WinoGeom ge = wino_geom(p, 4, 2 * W4T);                             // whole 64-tile workgroup tiles
+    if (!wino_extents_ok(p, 36, ge.Mt_pad)) return false;
+    const W4Plan w4 = wino4_gemm_plan(p, ge, slab_floats);
+    if (wino4_mode() < 2 && w4.judge_wg < min_wg) return false;              // too few workgroups: F(2x2) with its split-K is better
+    const size_t need = (size_t)36 * p.Cin * ge.Mt_pad;
+    if (need > v_cap) return false;
     cp.family = CONV_WINO4;
+    cp.geo = ge; cp.w4 = w4;
     cp.v_floats = need;
-    cp.w4 = wino4_gemm_plan(p, slab_floats);
-    cp.n_in = cp.n_gemm = cp.w4.chunks; cp.reduce = cp.w4.pieces > 1;
+    cp.n_in = cp.n_gemm = w4.chunks; cp.reduce = w4.pieces > 1;
     cp.fl_exec = 2.0 * (double)need * p.N;
     return true;
 }
@@ -598,17 +572,10 @@ bool wino4_plan(const ConvP &p, int min_wg, size_t v_cap, size_t slab_floats, Co
 void wino4_launch(const ConvP &p, const ConvPlan &cp, float *V, hipStream_t s, hipEvent_t *const *ev_in, hipEvent_t *const *ev_gemm,
                   hipEvent_t *ev_red) {
     const W4Plan &pl = cp.w4;
-    const int TH = (p.OH + 3) / 4, TW = (p.OW + 3) / 4;
-    const int Mt = pl.Mt, Mt_pad = pl.Mt_pad, KB = p.Cin / 8;
-    Wino4G g{};
-    g.V = V; g.U = p.wino4_u;
-    g.v_bytes = (unsigned)((size_t)36 * p.Cin * Mt_pad * 4);
-    g.u_bytes = (unsigned)((size_t)36 * p.Cin * p.N * 4);
-    g.Mt = Mt; g.Mt_pad = Mt_pad; g.KB = KB; g.N = p.N;
-    g.TH = TH; g.TW = TW; g.OH = p.OH; g.OW = p.OW; g.B = p.B; g.M = p.M;
-    g.bias = p.bias; g.res = p.res; g.res_bs = p.res_bs; g.res_bmod = p.res_bmod; g.y = p.y; g.y_bs = p.y_bs; g.relu_out = p.relu_out;
+    const WinoGeom &ge = cp.geo;
     const int tiles_n = pl.tiles_n, mb = pl.mb, tiles_m = pl.tiles_m;
-    g.fd_tpi = fastdiv_make((unsigned)(TH * TW)); g.fd_tw = fastdiv_make((unsigned)TW); g.fd_tiles_n = fastdiv_make((unsigned)tiles_n);
+    Wino4G g{};
+    wino_fill_desc(g, p, ge, 36, V, p.wino4_u, tiles_n);
     g.full_wg = pl.full_wg; g.pieces = pl.pieces; g.kb_per_piece = pl.per; g.partial = p.partial;
     g.xb_m = g.xb_n = g.xb_cols = 0;
     {   // 2-D XCD blocks for the whole-tile workgroups of an unchunked launch: 8 equal blocks that tile the (rows x tiles_n) grid
@@ -628,18 +595,11 @@ void wino4_launch(const ConvP &p, const ConvPlan &cp, float *V, hipStream_t s, h
     const size_t lds = (size_t)36 * W4T * W4N * sizeof(float);
     for (int c = 0; c < pl.chunks; ++c) {
         const int tm_lo = c * pl.tm_per_chunk, tm_hi = tm_lo + pl.tm_per_chunk < tiles_m ? tm_lo + pl.tm_per_chunk : tiles_m;
-        const int tile_lo = tm_lo * W4T * mb, tile_hi = pl.chunks == 1 ? Mt_pad : tm_hi * W4T * mb;
+        const int tile_lo = tm_lo * W4T * mb, tile_hi = pl.chunks == 1 ? ge.Mt_pad : tm_hi * W4T * mb;
         hipEvent_t *ei = ev_in ? ev_in[c] : nullptr, *eg = ev_gemm ? ev_gemm[c] : nullptr;
-        {
-            const unsigned gx = (unsigned)((8L * (tile_hi - tile_lo) + 255) / 256);
-            const int NCB = p.Cin / 32;
-            int chunks = (int)((2048 + gx - 1) / gx);
-            chunks = chunks < 1 ? 1 : (chunks > NCB ? NCB : chunks);
-            const int per = (NCB + chunks - 1) / chunks;
-            chunks = (NCB + per - 1) / per;
-            launch(wino4_input_kernel, dim3(gx, chunks), dim3(256), 0, s, ei, p.x0, p.x0_bytes, p.bs0, p.H, p.W, p.Cin, p.relu_in, TH, TW, Mt,
-                   Mt_pad, per, tile_lo, tile_hi, V);
-        }
+        const WinoInGrid ig = wino_input_grid(tile_hi - tile_lo, p.Cin);
+        launch(wino4_input_kernel, dim3(ig.gx, ig.chunks), dim3(256), 0, s, ei, p.x0, p.x0_bytes, p.bs0, p.H, p.W, p.Cin, p.relu_in, ge.TH, ge.TW,
+               ge.Mt, ge.Mt_pad, ig.per, tile_lo, tile_hi, V);
         g.tm0 = tm_lo;
         if (mb == 2) {
             const int grid = (tm_hi - tm_lo) * tiles_n;
@@ -651,8 +611,7 @@ void wino4_launch(const ConvP &p, const ConvPlan &cp, float *V, hipStream_t s, h
     }
 }
 
-// U [36][Cin/8][N][8] from the BN-folded direct weights w [N][Kp] (k = (ky*3 + kx) * Cin + c), on the host in double;
-// G of the points {0, 3/4, -3/4, 3/2, -3/2, inf}
+// U [36][Cin/8][N][8]; G of the points {0, 3/4, -3/4, 3/2, -3/2, inf}
 void wino4_transform_weights(const float *w, int N, int Cin, int Kp, float *U) {
     static const double G[6][3] = {{64.0 / 81, 0, 0},
                                    {-128.0 / 243, -32.0 / 81, -8.0 / 27},
@@ -660,20 +619,7 @@ void wino4_transform_weights(const float *w, int N, int Cin, int Kp, float *U) {
                                    {32.0 / 243, 16.0 / 81, 8.0 / 27},
                                    {32.0 / 243, -16.0 / 81, 8.0 / 27},
                                    {0, 0, 1}};
-    const int KB = Cin / 8;
-    for (int n = 0; n < N; ++n)
-        for (int c = 0; c < Cin; ++c) {
-            double g[3][3], tmp[6][3];
-            for (int ky = 0; ky < 3; ++ky)
-                for (int kx = 0; kx < 3; ++kx) g[ky][kx] = w[(size_t)n * Kp + (size_t)(ky * 3 + kx) * Cin + c];
-            for (int i = 0; i < 6; ++i)
-                for (int kx = 0; kx < 3; ++kx) tmp[i][kx] = G[i][0] * g[0][kx] + G[i][1] * g[1][kx] + G[i][2] * g[2][kx];
-            for (int i = 0; i < 6; ++i)
-                for (int j = 0; j < 6; ++j) {
-                    const double u = tmp[i][0] * G[j][0] + tmp[i][1] * G[j][1] + tmp[i][2] * G[j][2];
-                    U[((((size_t)(i * 6 + j) * KB + c / 8) * N + n) << 3) + (c & 7)] = (float)u;
-                }
-        }
+    wino_transform_weights_with(G, w, N, Cin, Kp, U);
 }
 
 #ifdef STCN_W4_CLOCK

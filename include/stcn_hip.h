@@ -144,6 +144,14 @@ int stcn_test_conv(void *stream, const float *x, const float *w, const float *bi
 /* Test hook: the kernel family and plan stcn_test_conv would run this shape as (the string stcn_last_conv_path() gives after it), from
  * the host-side planners alone: nothing is allocated on a device, nothing is launched, no GPU is needed.  out: n bytes. */
 int stcn_test_conv_path(int B, int H, int W, int Cin, int Cout, int K, int stride, int flags, int splitk, char *out, int n);
+/* Test hook: the same plan in numbers, under the same conditions (no GPU is needed).  iv (n >= STCN_CONV_PLAN_INTS int32):
+ *   family (0 literal, 1 fusion, 2 F(4x4), 3 F(2x2), 4 direct), splitk, ppw, tail, n_in, n_gemm, reduce;
+ *   Winograd tile geometry TH, TW, Mt, Mt_pad, KB, and F(2x2)'s kb_per_split;
+ *   F(4x4): mb, tiles_m, tiles_n, grid, full_wg, pieces, per, chunks, tm_per_chunk;
+ *   direct: tile_big, rem_full, rem_split, rem_per, chain
+ * - fields of other families than the plan's are zero.  dv (2 doubles): v_floats, fl_exec. */
+#define STCN_CONV_PLAN_INTS 27
+int stcn_test_conv_plan(int B, int H, int W, int Cin, int Cout, int K, int stride, int flags, int splitk, int32_t *iv, int n, double *dv);
 /* Which kernel family the calling thread's last convolution (stcn_test_conv, or the last conv an interact() enqueued) ran as:
  * "direct splitk=1", "direct_pointwise splitk=1", "direct_narrow ...", "direct_smallc ...", "direct_big ...", "... +tail ...",
  * "wino2 ppw=1 splitk=2" (Winograd F(2x2,3x3)), "wino4 chunks=2 +tail" (F(4x4,3x3)), "fusion_wino", "fusion_direct", "n1".
