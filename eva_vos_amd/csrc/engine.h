@@ -52,6 +52,7 @@ struct Model {
     std::map<std::string, ConvW> conv;
     CbamW cbam{};
     bool has_fuse = false;
+    int top_k = MEMREAD_MAX_TOPK;          // rows per query of the memory read (PropagationNetwork(top_k=...), prop_net.py:141)
     int wino4_min_wg = 100;                // fewest 32 x 32 workgroups for which a flagged layer takes the F(4x4) kernel (tests: 0)
     std::vector<void *> allocs;
     const ConvW &c(const std::string &name) const;

@@ -234,15 +234,23 @@ int stcn_test_encode_value(const stcn_model *m, void *stream, const float *img, 
 
 int stcn_test_memory_read(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k,
                           int32_t *topk_idx, float *topk_w, float *readout) {
-    if (!mk || !mv || !qk || !readout || N < 50 || Q < 1 || k < 1) { set_error("stcn_test_memory_read: bad arguments (N >= 50)"); return STCN_E_INVALID; }
+    return stcn_test_memory_read_k(stream, mk, mv, qk, N, Q, k, STCN_MAX_TOP_K, topk_idx, topk_w, readout);
+}
+
+int stcn_test_memory_read_k(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k,
+                            int32_t *topk_idx, float *topk_w, float *readout) {
+    if (!mk || !mv || !qk || !readout || top_k < 1 || top_k > STCN_MAX_TOP_K || N < top_k || Q < 1 || k < 1) {
+        set_error("stcn_test_memory_read: bad arguments (1 <= top_k <= %d, N >= top_k; top_k=%d N=%d)", STCN_MAX_TOP_K, top_k, N);
+        return STCN_E_INVALID;
+    }
     hipStream_t s = (hipStream_t)stream;
     DevBuf msq, cv, ci, cn, gm, tau;
     const size_t pairs = memread_list_pairs(Q);
-    RC(msq.alloc(N + 64)); RC(cv.alloc(pairs * 50)); RC(ci.alloc(pairs * 50)); RC(cn.alloc(pairs));
+    RC(msq.alloc(N + 64)); RC(cv.alloc(pairs * MEMREAD_MAX_TOPK)); RC(ci.alloc(pairs * MEMREAD_MAX_TOPK)); RC(cn.alloc(pairs));
     RC(gm.alloc(pairs * 64)); RC(tau.alloc(Q));
     HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(N + 64) * 4, s));
     rowsumsq_launch(mk, N, 64, msq.p, s);
-    memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, readout, (long)Q * 512, topk_idx, topk_w,
+    memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, topk_idx, topk_w,
                        MemReadScratch{cv.p, reinterpret_cast<int32_t *>(ci.p), reinterpret_cast<int32_t *>(cn.p), gm.p, tau.p}, s);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
@@ -253,11 +261,19 @@ int stcn_test_memory_read(void *stream, const float *mk, const float *mv, const 
 // two HIP events on `stream`; scratch is allocated once, outside the timed region.  ms = average per read.
 int stcn_bench_memory_read(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int iters,
                            float *readout, float *ms, int32_t *plan7) {
-    if (!mk || !mv || !qk || !readout || !ms || N < 50 || Q < 1 || k < 1 || iters < 1) { set_error("stcn_bench_memory_read: bad arguments"); return STCN_E_INVALID; }
+    return stcn_bench_memory_read_k(stream, mk, mv, qk, N, Q, k, STCN_MAX_TOP_K, iters, readout, ms, plan7);
+}
+
+int stcn_bench_memory_read_k(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k, int iters,
+                             float *readout, float *ms, int32_t *plan7) {
+    if (!mk || !mv || !qk || !readout || !ms || top_k < 1 || top_k > STCN_MAX_TOP_K || N < top_k || Q < 1 || k < 1 || iters < 1) {
+        set_error("stcn_bench_memory_read: bad arguments (1 <= top_k <= %d, N >= top_k; top_k=%d N=%d)", STCN_MAX_TOP_K, top_k, N);
+        return STCN_E_INVALID;
+    }
     hipStream_t s = (hipStream_t)stream;
     DevBuf msq, cv, ci, cn, gm, tau;
     const size_t pairs = memread_list_pairs(Q);
-    RC(msq.alloc(N + 64)); RC(cv.alloc(pairs * 50)); RC(ci.alloc(pairs * 50)); RC(cn.alloc(pairs));
+    RC(msq.alloc(N + 64)); RC(cv.alloc(pairs * MEMREAD_MAX_TOPK)); RC(ci.alloc(pairs * MEMREAD_MAX_TOPK)); RC(cn.alloc(pairs));
     RC(gm.alloc(pairs * 64)); RC(tau.alloc(Q));
     HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(N + 64) * 4, s));
     rowsumsq_launch(mk, N, 64, msq.p, s);
@@ -265,10 +281,10 @@ int stcn_bench_memory_read(void *stream, const float *mk, const float *mv, const
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     for (int it = 0; it < 2; ++it)
-        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, readout, (long)Q * 512, nullptr, nullptr, scr, s);
+        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, nullptr, nullptr, scr, s);
     HIPCHK(hipEventRecord(e0, s));
     for (int it = 0; it < iters; ++it)
-        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, readout, (long)Q * 512, nullptr, nullptr, scr, s);
+        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, nullptr, nullptr, scr, s);
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipEventSynchronize(e1));
     HIPCHK(hipEventElapsedTime(ms, e0, e1));

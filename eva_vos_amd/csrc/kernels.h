@@ -215,7 +215,9 @@ void cbam_launch(const float *x, float *out, int B, int h, int w, const CbamW &c
                  hipStream_t s);
 
 // ---------------------------------------------------------------- space-time memory read
-// launch plan of the top-50 read: `steps` 64-row steps of the bank; pass 1 visits every ss-th step (ns of them) in nc1 chunks of
+// the largest top_k the read is built for (every capacity below is sized for it; STCN_MAX_TOP_K of the C ABI) and the default model's
+constexpr int MEMREAD_MAX_TOPK = 50;
+// launch plan of the top-k read (it does not depend on top_k): `steps` 64-row steps of the bank; pass 1 visits every ss-th step (ns of them) in nc1 chunks of
 // spc1 sampled steps, pass 2 all steps in nc2 chunks of spc2
 struct MemReadPlan { int steps, ss, ns, nc1, spc1, nc2, spc2; };
 MemReadPlan memread_plan(int N, int Q);
@@ -236,9 +238,9 @@ static inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_
 }
 #endif
 // mk [N,64], msq [N] (+ >= 64 readable floats of padding), qk [Q,64]; mv [k][N][512] with object stride mv_os; readout [k][Q][512] with
-// object stride ro_os.  topk_idx/topk_w optional outputs [Q,50].
+// object stride ro_os.  top_k: 1 .. MEMREAD_MAX_TOPK rows per query, N >= top_k.  topk_idx/topk_w optional outputs [Q,top_k].
 void memory_read_launch(const float *mk, const float *msq, const float *qk, int N, int Q,
-                        const float *mv, long mv_os, int k, float *readout, long ro_os,
+                        const float *mv, long mv_os, int k, int top_k, float *readout, long ro_os,
                         int32_t *topk_idx, float *topk_w, MemReadScratch scr, hipStream_t s);
 // fusion attention read: mk,qk [hw,64]; pos,neg [kk][16h*16w planes] -> attn [kk][2][nh*nw]; pooled: scratch of attention_nchp(2 kk) * h * w floats
 struct AttnScratch { float *gmax, *cmax, *part; };   // [256][hw], [hw], attention_part_floats(kk, hw) ([16][hw][19] up to 8 objects)
@@ -265,8 +267,8 @@ void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, co
                         int Tn, int H, int W, int radius, double no_object, uint8_t *gen, uint8_t *bmap, int *counts, int T_all, double *quality,
                         int *select, hipStream_t s, int t0);
 
-// debug/stress: launch ONLY the merge stage on prepared candidate lists (cand_v/cand_i [NC][Q][50])
-void merge_only_launch(const float *cand_v, const int32_t *cand_i, int NC, int Q, const float *mv, long mv_os, int k,
+// debug/stress: launch ONLY the merge stage on prepared candidate lists (cand_v/cand_i [NC][Q][50], top_k entries used of each)
+void merge_only_launch(const float *cand_v, const int32_t *cand_i, int NC, int Q, const float *mv, long mv_os, int k, int top_k,
                        float *readout, long ro_os, hipStream_t s);
 
 // pure fp32-MFMA load (no memory traffic): launches `grid` workgroups of 12 waves x iters x 12 MFMAs, returns the FLOP of the launch

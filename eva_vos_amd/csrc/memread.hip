@@ -1,6 +1,7 @@
 // memread.hip - space-time memory read of STCN on gfx950:
 //   affinity S = (2 mk.qk - |mk|^2 - |qk|^2)/sqrt(64)          (reference prop_net.py:80-90)
-//   per query column: top-50 over the T*H*W memory rows, softmax over the 50 (prop_net.py:53-60)
+//   per query column: top-K over the T*H*W memory rows, softmax over the K (prop_net.py:53-60); K = the model's top_k
+//     (prop_net.py:141), 1 .. 50, 50 in the description below
 //   readout = sum_j w_j * mv[idx_j]                             (prop_net.py:108-115)
 // The reference materialises the dense [T*HW x HW] affinity and multiplies by the dense matrix; here S
 // only ever lives in registers.  Exact two-pass selection:
@@ -17,6 +18,11 @@
 //   merge_readout: one wave per query merges the chunk lists, softmaxes the 50 with wavefront
 //     reductions and gathers 50 value rows (2 KB each, NHWC bank) per object.
 //   The column-constant -|qk|^2 term cancels in exp(v - v_max) and is dropped.
+// top_k: a wave-uniform kernel argument K (1 .. TOPK = 50) of every kernel that depends on the cut - the selects compare counts with it,
+//   the softmax and the gathers run over K lanes / rows.  A compile-time 50 beside it was measured and bought nothing (profiles/topk_default_ab.txt:
+//   the read and the headline are the same within the repeats of one box), so there is ONE instantiation.  Every capacity is sized for 50 and
+//   does not move: candidate lists keep a stride of 50, CAP2 = 64 stays above the cut, merge_readout stages MAXCHUNK2 * 50 entries, one lane
+//   per selected row.  top_k = None of the reference (a dense softmax over the whole bank) is another kernel family and is not built.
 #include <cstdlib>
 #include <type_traits>
 
@@ -26,7 +32,7 @@ namespace stcn {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-static constexpr int TOPK = 50;
+static constexpr int TOPK = MEMREAD_MAX_TOPK;   // the largest cut, the default model's, and the stride of every candidate list
 static constexpr int CAP = 128;       // per-(query, chunk) candidate list capacity (>= TOPK + 64)
 static constexpr int TROWS = 128;     // memory rows per tile of the attention read
 static constexpr int HROWS = 64;      // rows per step of the top-k passes
@@ -49,10 +55,10 @@ __device__ __forceinline__ int lanes_below(unsigned long long m, int lane) {
 }
 __device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// Keep the best TOPK of the n (<= 128) entries of a wave-owned list (values lv, payload li): bitwise
+// Keep the best K of the n (K <= n <= 128) entries of a wave-owned list (values lv, payload li): bitwise
 // radix select on order-preserving keys (ballot + popcount per bit), ties by list position.
-// Returns the TOPK-th best value; the list is compacted to exactly TOPK entries.
-__device__ __forceinline__ float wave_select128(float *lv, int *li, int n, int lane) {
+// Returns the K-th best value; the list is compacted to exactly K entries.
+__device__ __forceinline__ float wave_select128(float *lv, int *li, int n, int lane, const int K) {
     lds_fence();
     const float f0 = lane < n ? lv[lane] : 0.f, f1 = lane + 64 < n ? lv[lane + 64] : 0.f;
     const int i0 = lane < n ? li[lane] : 0, i1 = lane + 64 < n ? li[lane + 64] : 0;
@@ -61,11 +67,11 @@ __device__ __forceinline__ float wave_select128(float *lv, int *li, int n, int l
     for (int bit = 31; bit >= 0; --bit) {
         const unsigned cand = prefix | (1u << bit);
         const int c = __popcll(__ballot(k0 >= cand)) + __popcll(__ballot(k1 >= cand));
-        if (c >= TOPK) prefix = cand;
+        if (c >= K) prefix = cand;
     }
     const unsigned long long g0 = __ballot(k0 > prefix), g1 = __ballot(k1 > prefix);
     const unsigned long long e0 = __ballot(k0 == prefix), e1 = __ballot(k1 == prefix);
-    const int need = TOPK - (__popcll(g0) + __popcll(g1));              // >= 1 ties to keep
+    const int need = K - (__popcll(g0) + __popcll(g1));                 // >= 1 ties to keep
     const bool keep0 = (k0 > prefix) || (k0 == prefix && lanes_below(e0, lane) < need);
     const bool keep1 = (k1 > prefix) || (k1 == prefix && __popcll(e0) + lanes_below(e1, lane) < need);
     const unsigned long long b0 = __ballot(keep0), b1 = __ballot(keep1);
@@ -138,11 +144,12 @@ static constexpr int KT_FLOATS = HROWS * 64 + HROWS;                    // key t
 static constexpr int LISTS_PER_WAVE = 2 * 16 * CAP2 + 32;               // LV, LI, CNT, TAU
 static constexpr int NGRP2 = 64;                                        // pass-1 maxima per query per chunk
 
+//   K: the cut of pass 2 (1 .. TOPK, wave-uniform).  Pass 1 does not depend on it.
 template <bool COLLECT, bool SINGLE = false>
 __global__ __launch_bounds__(256, SINGLE ? 3 : 2) void affinity_tile_kernel(
     const float *__restrict__ mk, const float *__restrict__ msq, const float *__restrict__ qk, int N, int Q, int ns,
     int ss, int spc, float *__restrict__ gmax, const float *__restrict__ tau_in, float *__restrict__ cand_v,
-    int32_t *__restrict__ cand_i, int32_t *__restrict__ cand_n) {
+    int32_t *__restrict__ cand_i, int32_t *__restrict__ cand_n, const int K) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     constexpr int NBUF = SINGLE ? 1 : 2;                                // SINGLE: one key tile buffer, two barriers per step, 3 workgroups per CU
@@ -258,7 +265,7 @@ __global__ __launch_bounds__(256, SINGLE ? 3 : 2) void affinity_tile_kernel(
             // Optimistic appends, one accumulator register at a time and only where some lane of the wave passes its
             // threshold (a compare + a scalar branch otherwise): take a list position with an LDS atomic, store if it is
             // inside the list.  An append that finds its list full is remembered in `drop` and replayed after the list has
-            // been cut back to its best TOPK (which also raises that query's threshold): no overflow check on the way.
+            // been cut back to its best K (which also raises that query's threshold): no overflow check on the way.
             unsigned drop = 0;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -283,8 +290,8 @@ __global__ __launch_bounds__(256, SINGLE ? 3 : 2) void affinity_tile_kernel(
                 while (fq) {                                             // a list with drops holds exactly CAP2 entries
                     const int jj = __builtin_ctz(fq);
                     fq &= fq - 1;
-                    const float tt = wave_select128(LV + jj * CAP2, LI + jj * CAP2, CAP2, lane);
-                    if (lane == 0) { CNT[jj] = TOPK; TAU[jj] = fmaxf(TAU[jj], tt); }
+                    const float tt = wave_select128(LV + jj * CAP2, LI + jj * CAP2, CAP2, lane, K);
+                    if (lane == 0) { CNT[jj] = K; TAU[jj] = fmaxf(TAU[jj], tt); }
                     lds_fence();
                 }
                 tcol = TAU[col];
@@ -331,13 +338,13 @@ __global__ __launch_bounds__(256, SINGLE ? 3 : 2) void affinity_tile_kernel(
         }
         return;
     }
-    // chunk winners -> global: cand_n[chunk][q] entries of cand_v / cand_i[chunk][q][TOPK]
+    // chunk winners -> global: cand_n[chunk][q] (<= K) entries of cand_v / cand_i[chunk][q][TOPK]
     lds_fence();
     for (int jj = 0; jj < 16; ++jj) {
         float *lv = LV + jj * CAP2;
         int *li = LI + jj * CAP2;
         int cnt = __builtin_amdgcn_readfirstlane(CNT[jj]);
-        if (cnt > TOPK) { wave_select128(lv, li, cnt, lane); cnt = TOPK; }
+        if (cnt > K) { wave_select128(lv, li, cnt, lane, K); cnt = K; }
         lds_fence();
         const int q = q0 + jj;
         if (q < Q) {
@@ -387,9 +394,9 @@ __global__ __launch_bounds__(64 * WAVES) void colmax_pass_kernel(
     }
 }
 
-// tau[q] = TOPK-th largest of the G group maxima of query q (-inf when fewer than TOPK are finite); G <= 512
+// tau[q] = K-th largest of the G group maxima of query q (-inf when fewer than K are finite); G <= 512
 __global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict__ gmax, int G, int Q,
-                                                        float *__restrict__ tau) {
+                                                        float *__restrict__ tau, const int K) {
     const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= Q) return;
@@ -406,17 +413,17 @@ __global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict_
         int c = 0;
 #pragma unroll
         for (int e = 0; e < 8; ++e) c += __popcll(__ballot(k[e] >= cand));
-        if (c >= TOPK) prefix = cand;
+        if (c >= K) prefix = cand;
     }
-    // prefix == 0: fewer than TOPK finite maxima -> no usable bound.  The bound must stay BELOW the
-    // TOPK-th best (the filter keeps v > tau): step one key down.
-    // ... and lowered by the re-score window: a row whose fp32 score lies a few ulps BELOW the 50th may beat it in exact arithmetic;
+    // prefix == 0: fewer than K finite maxima -> no usable bound.  The bound must stay BELOW the
+    // K-th best (the filter keeps v > tau): step one key down.
+    // ... and lowered by the re-score window: a row whose fp32 score lies a few ulps BELOW the K-th may beat it in exact arithmetic;
     // it has to reach the merge kernel's candidate list to be re-scored (merge_readout_kernel: RESCORE_W)
     if (lane == 0) tau[q] = prefix == 0u ? -__builtin_inff() : key2f(prefix - 1u) - 1.5f * RESCORE_W;
 }
 
-// one wave per query: merge the chunk lists (cand_n[c][q] entries each; cand_n == nullptr: TOPK each, -inf = missing),
-// softmax, sparse readout
+// one wave per query: merge the chunk lists (cand_n[c][q] entries each; cand_n == nullptr: K each, -inf = missing),
+// softmax, sparse readout.  K = top_k; the lists keep their stride of TOPK, topk_idx / topk_w are [Q][K]
 // Near-tie re-score (round 5): two fp32 implementations of the affinity differ by ~1e-5 (64-term dot products of |S| ~ 100: one ulp is
 // 7.6e-6), so a query whose 50th and 51st scores lie closer than that gets another row set from every implementation - the reference's
 // own thread counts included.  With `mk` / `qk` given, the candidates whose fp32 score lies within RESCORE_W of the
@@ -440,7 +447,7 @@ __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restr
                                                             const float *__restrict__ mv, long mv_os, int k,
                                                             float *__restrict__ readout, long ro_os,
                                                             int32_t *__restrict__ topk_idx, float *__restrict__ topk_w,
-                                                            const float *__restrict__ mk, const float *__restrict__ qk) {
+                                                            const float *__restrict__ mk, const float *__restrict__ qk, const int K) {
     __shared__ float s_v[4][MAXCHUNK2 * TOPK];
     __shared__ int s_i[4][MAXCHUNK2 * TOPK];
     __shared__ float s_w[4][64];
@@ -451,7 +458,7 @@ __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restr
     float *sv = s_v[wave];
     int *si = s_i[wave];
     // list sizes -> offsets (lane c owns chunk c; NC <= 64), then all entries with independent loads
-    int nl = lane < NC ? (cand_n ? cand_n[(long)lane * Q + q] : TOPK) : 0;
+    int nl = lane < NC ? (cand_n ? cand_n[(long)lane * Q + q] : K) : 0;
     int ol = nl;
     for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(ol, o); if (lane >= o) ol += u; }
     const int n = __shfl(ol, 63);
@@ -465,14 +472,14 @@ __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restr
         }
     }
     lds_fence();
-    // bitwise radix select of the TOPK-th largest key over n entries
+    // bitwise radix select of the K-th largest key over n entries
     unsigned prefix = 0;
     for (int bit = 31; bit >= 0; --bit) {
         const unsigned cand = prefix | (1u << bit);
         int c = 0;
         for (int e = lane; e < n; e += 64) c += f2key(sv[e]) >= cand ? 1 : 0;
         for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-        if (c >= TOPK) prefix = cand;
+        if (c >= K) prefix = cand;
     }
     // compact winners (ties: first in list order) into s_w / s_x
     int base = 0;
@@ -524,7 +531,7 @@ __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restr
                 if (keep) { const int pp = base + lanes_below(kb, lane); s_w[wave][pp] = sv[e]; s_x[wave][pp] = si[e]; }
                 base += __popcll(kb);
             }
-            const bool keepn = lane < nnear && rank < TOPK - nab;
+            const bool keepn = lane < nnear && rank < K - nab;
             const unsigned long long kn = __ballot(keepn);
             if (keepn) { const int pp = base + lanes_below(kn, lane); s_w[wave][pp] = mv_; s_x[wave][pp] = row; }
         }
@@ -533,7 +540,7 @@ __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restr
         int ngt = 0;
         for (int e = lane; e < n; e += 64) ngt += f2key(sv[e]) > prefix ? 1 : 0;
         for (int o = 32; o > 0; o >>= 1) ngt += __shfl_xor(ngt, o);
-        int need = TOPK - ngt;
+        int need = K - ngt;
         for (int e0 = 0; e0 < n; e0 += 64) {
             const int e = e0 + lane;
             const unsigned key = e < n ? f2key(sv[e]) : 0u;
@@ -551,19 +558,19 @@ __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restr
         }
     }
     lds_fence();
-    // softmax over the 50 (exp(v - max) / sum), wavefront reductions
-    const float v = lane < TOPK ? s_w[wave][lane] : -__builtin_inff();
+    // softmax over the K (exp(v - max) / sum), wavefront reductions
+    const float v = lane < K ? s_w[wave][lane] : -__builtin_inff();
     float mx = v;
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    const float ex = lane < TOPK ? expf(v - mx) : 0.f;
+    const float ex = lane < K ? expf(v - mx) : 0.f;
     float sum = ex;
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
     const float wgt = ex / sum;
     lds_fence();
-    if (lane < TOPK) {
+    if (lane < K) {
         s_w[wave][lane] = wgt;
-        if (topk_idx) topk_idx[(long)q * TOPK + lane] = s_x[wave][lane];
-        if (topk_w) topk_w[(long)q * TOPK + lane] = wgt;
+        if (topk_idx) topk_idx[(long)q * K + lane] = s_x[wave][lane];
+        if (topk_w) topk_w[(long)q * K + lane] = wgt;
     }
     lds_fence();
     // gather: lane covers channels [4*lane, +4) and [256 + 4*lane, +4) of each 512-float value row
@@ -571,7 +578,7 @@ __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restr
         const float *mvo = mv + (long)o * mv_os;
         f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 5
-        for (int j = 0; j < TOPK; ++j) {
+        for (int j = 0; j < K; ++j) {
             const float wj = s_w[wave][j];
             const float *row = mvo + (long)s_x[wave][j] * 512 + 4 * lane;
             const f32x4 r0 = *reinterpret_cast<const f32x4 *>(row);
@@ -586,29 +593,42 @@ __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restr
 }
 
 // k > 1: the gather of merge_readout_kernel, one wave per (query, OBJECT) instead of one per query looping over the objects
-// (5x the waves in flight for the 50 x 2 KB random rows per query and object; the merge kernel then only selects and
-// softmaxes and leaves idx / weights [Q][50] in scratch).  4 rows (8 loads of 16 B) in flight per wave: on random rows of a 1.7 GB
+// (5x the waves in flight for the K x 2 KB random rows per query and object; the merge kernel then only selects and
+// softmaxes and leaves idx / weights [Q][K] in scratch).  4 rows (8 loads of 16 B) in flight per wave: on random rows of a 1.7 GB
 // bank 10 in flight were 1.7 % slower (round 5: 0.6125 vs 0.6229 ms per read at T = 104, k = 5; an object-interleaved bank with the k
 // object waves of a query side by side 0.631 - no better: the rows are 2 KB, a DRAM page either way)
 __global__ __launch_bounds__(256) void gather_readout_kernel(const int32_t *__restrict__ idx, const float *__restrict__ w, int Q,
                                                              const float *__restrict__ mv, long mv_os, float *__restrict__ readout,
-                                                             long ro_os) {
+                                                             long ro_os, const int K) {
     const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= Q) return;
     const float *mvo = mv + (long)blockIdx.y * mv_os + 4 * lane;
-    const int myi = lane < TOPK ? idx[(long)q * TOPK + lane] : 0;
-    const float myw = lane < TOPK ? w[(long)q * TOPK + lane] : 0.f;
+    const int myi = lane < K ? idx[(long)q * K + lane] : 0;
+    const float myw = lane < K ? w[(long)q * K + lane] : 0.f;
     f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int j = 0; j < TOPK; ++j) {
-        const float wj = __shfl(myw, j);
-        const float *row = mvo + (long)__shfl(myi, j) * 512;
-        const f32x4 r0 = *reinterpret_cast<const f32x4 *>(row);
-        const f32x4 r1 = *reinterpret_cast<const f32x4 *>(row + 256);
-        a0 += r0 * wj;
-        a1 += r1 * wj;
-    }
+    // rows in selection order, blocks of 4 with all 8 loads requested before the first use, then the K % 4 last rows one by one (the cut is
+    // a run-time value and the shuffles are convergent operations: the compiler does not unroll `for (j < K)` by itself)
+    auto rows = [&](const int j, auto nc) {
+        constexpr int n = decltype(nc)::value;
+        f32x4 r0[n], r1[n];
+        float wj[n];
+#pragma unroll
+        for (int u = 0; u < n; ++u) {
+            wj[u] = __shfl(myw, j + u);
+            const float *row = mvo + (long)__shfl(myi, j + u) * 512;
+            r0[u] = *reinterpret_cast<const f32x4 *>(row);
+            r1[u] = *reinterpret_cast<const f32x4 *>(row + 256);
+        }
+#pragma unroll
+        for (int u = 0; u < n; ++u) {
+            a0 += r0[u] * wj[u];
+            a1 += r1[u] * wj[u];
+        }
+    };
+    int j = 0;
+    for (; j + 4 <= K; j += 4) rows(j, std::integral_constant<int, 4>{});
+    for (; j < K; ++j) rows(j, std::integral_constant<int, 1>{});
     float *dst = readout + (long)blockIdx.y * ro_os + (long)q * 512 + 4 * lane;
     *reinterpret_cast<f32x4 *>(dst) = a0;
     *reinterpret_cast<f32x4 *>(dst + 256) = a1;
@@ -643,7 +663,7 @@ MemReadPlan memread_plan(int N, int Q) {
 size_t memread_list_pairs(int Q) { return (size_t)65536 + (size_t)Q + 64; }
 
 void memory_read_launch(const float *mk, const float *msq, const float *qk, int N, int Q, const float *mv,
-                        long mv_os, int k, float *readout, long ro_os, int32_t *topk_idx, float *topk_w,
+                        long mv_os, int k, int top_k, float *readout, long ro_os, int32_t *topk_idx, float *topk_w,
                         MemReadScratch scr, hipStream_t s) {
     const MemReadPlan pl = memread_plan(N, Q);
     const int qblocks = (Q + 63) / 64;
@@ -653,28 +673,28 @@ void memory_read_launch(const float *mk, const float *msq, const float *qk, int 
     const size_t lds2 = (single ? lds1 / 2 : lds1) + (size_t)4 * LISTS_PER_WAVE * sizeof(float);
     allow_big_lds(reinterpret_cast<const void *>(&affinity_tile_kernel<true, true>), lds2);
     hipLaunchKernelGGL((affinity_tile_kernel<false>), dim3(qblocks, pl.nc1), dim3(256), lds1, s, mk, msq, qk, N, Q, pl.ns, pl.ss,
-                       pl.spc1, scr.gmax, (const float *)nullptr, (float *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
-    hipLaunchKernelGGL(threshold_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.gmax, pl.nc1 * NGRP2, Q, scr.tau);
+                       pl.spc1, scr.gmax, (const float *)nullptr, (float *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, top_k);
+    hipLaunchKernelGGL(threshold_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.gmax, pl.nc1 * NGRP2, Q, scr.tau, top_k);
     hipLaunchKernelGGL((affinity_tile_kernel<true, true>), dim3(qblocks, pl.nc2), dim3(256), lds2, s, mk, msq, qk, N, Q, pl.steps, 1,
-                       pl.spc2, (float *)nullptr, scr.tau, scr.cand_v, scr.cand_i, scr.cand_n);
+                       pl.spc2, (float *)nullptr, scr.tau, scr.cand_v, scr.cand_i, scr.cand_n, top_k);
     if (k == 1 || topk_idx || topk_w) {
         hipLaunchKernelGGL(merge_readout_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.cand_v, scr.cand_i, scr.cand_n, pl.nc2, Q,
-                           mv, mv_os, k, readout, ro_os, topk_idx, topk_w, rescore ? mk : nullptr, qk);
+                           mv, mv_os, k, readout, ro_os, topk_idx, topk_w, rescore ? mk : nullptr, qk, top_k);
         return;
     }
-    // several objects: merge once per query (indices / weights into the group-maxima scratch, free since threshold_kernel),
+    // several objects: merge once per query (indices / weights [Q][top_k] into the group-maxima scratch, free since threshold_kernel),
     // then gather with one wave per (query, object)
     int32_t *gi = reinterpret_cast<int32_t *>(scr.gmax);
     float *gw = scr.gmax + (size_t)Q * TOPK;
     hipLaunchKernelGGL(merge_readout_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.cand_v, scr.cand_i, scr.cand_n, pl.nc2, Q,
-                       mv, mv_os, 0, readout, ro_os, gi, gw, rescore ? mk : nullptr, qk);
-    hipLaunchKernelGGL(gather_readout_kernel, dim3((Q + 3) / 4, k), dim3(256), 0, s, gi, gw, Q, mv, mv_os, readout, ro_os);
+                       mv, mv_os, 0, readout, ro_os, gi, gw, rescore ? mk : nullptr, qk, top_k);
+    hipLaunchKernelGGL(gather_readout_kernel, dim3((Q + 3) / 4, k), dim3(256), 0, s, gi, gw, Q, mv, mv_os, readout, ro_os, top_k);
 }
 
-void merge_only_launch(const float *cand_v, const int32_t *cand_i, int NC, int Q, const float *mv, long mv_os, int k,
+void merge_only_launch(const float *cand_v, const int32_t *cand_i, int NC, int Q, const float *mv, long mv_os, int k, int top_k,
                        float *readout, long ro_os, hipStream_t s) {
     hipLaunchKernelGGL(merge_readout_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, cand_v, cand_i, (const int32_t *)nullptr, NC, Q,
-                       mv, mv_os, k, readout, ro_os, (int32_t *)nullptr, (float *)nullptr, (const float *)nullptr, (const float *)nullptr);
+                       mv, mv_os, k, readout, ro_os, (int32_t *)nullptr, (float *)nullptr, (const float *)nullptr, (const float *)nullptr, top_k);
 }
 
 // ------------------------------------------------------------------------------------------------

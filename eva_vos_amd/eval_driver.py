@@ -180,6 +180,7 @@ def main():
     ap.add_argument("--fusion-weights", default="./model_weights/mivos/fusion.pth")
     ap.add_argument("--qnet-weights", default="./model_weights/qnet/qnet.pth")
     ap.add_argument("--synthetic-weights", action="store_true", help="use the deterministic recipe (no checkpoints)")
+    ap.add_argument("--top-k", type=int, default=50, help="rows of the memory bank each query reads, 1..50 (PropagationNetwork(top_k=...): 20 for STCN checkpoints, 50 for MiVOS)")
     a = ap.parse_args()
     import torch.distributed as dist
 
@@ -187,7 +188,7 @@ def main():
     from .params import FusionNet, PropagationNetwork
     torch.set_grad_enabled(False)
     shard.init_from_env()                                  # one process per GPU; RCCL unless STCN_DIST_BACKEND says otherwise
-    prop, fuse, qnet = PropagationNetwork(), FusionNet(), None
+    prop, fuse, qnet = PropagationNetwork(top_k=a.top_k), FusionNet(), None
     if a.policy == "qnet_mask":
         from .qnet import QualityNet
         qnet = QualityNet()

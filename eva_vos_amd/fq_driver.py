@@ -560,6 +560,7 @@ def main():
     ap.add_argument("--synthetic-weights", action="store_true", help="use the deterministic recipe (no checkpoints)")
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--lanes", type=int, default=2, help="videos in flight per GPU")
+    ap.add_argument("--top-k", type=int, default=50, help="rows of the memory bank each query reads, 1..50 (PropagationNetwork(top_k=...): 20 for STCN checkpoints, 50 for MiVOS)")
     a = ap.parse_args()
     import torch.distributed as dist
 
@@ -567,7 +568,7 @@ def main():
     from .params import FusionNet, PropagationNetwork
     torch.set_grad_enabled(False)
     shard.init_from_env()                                  # one process per GPU; RCCL unless STCN_DIST_BACKEND says otherwise
-    prop, fuse = PropagationNetwork(), FusionNet()
+    prop, fuse = PropagationNetwork(top_k=a.top_k), FusionNet()
     if a.synthetic_weights:
         prop.load_state_dict(synth.recipe_state_dict(prop))
         fuse.load_state_dict(synth.recipe_state_dict(fuse))

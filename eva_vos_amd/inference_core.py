@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .params import check_top_k
 
 _MODEL_CACHE: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 _PINNED_DOWNLOAD = os.environ.get("STCN_PINNED_DOWNLOAD", "1") != "0"      # 0: the reference's plain .cpu() (measurement aid)
@@ -83,7 +84,7 @@ def _pinned_result(shape, live: list):
 class _Model:
     """Owns one ``stcn_model`` handle (BN-folded, repacked weights on one device)."""
 
-    def __init__(self, prop_net, fuse_net, device_index: int):
+    def __init__(self, prop_net, fuse_net, device_index: int, top_k: int = 50):
         lib = _lib.lib()
         keep = []
 
@@ -103,7 +104,8 @@ class _Model:
         p, n_p = descs(prop_net)
         f, n_f = descs(fuse_net) if fuse_net is not None else (None, 0)
         h = C.c_void_p()
-        _lib.check(lib.stcn_model_create(device_index, p, n_p, f, n_f, C.byref(h)), "stcn_model_create")
+        opts = _lib.ModelOpts(top_k=int(top_k))
+        _lib.check(lib.stcn_model_create_ex(device_index, p, n_p, f, n_f, C.byref(opts), C.byref(h)), "stcn_model_create_ex")
         self.handle = h
         self._finalizer = weakref.finalize(self, lib.stcn_model_destroy, h)
 
@@ -163,13 +165,26 @@ def release_pooled_memory() -> None:
     _lib.check(_lib.lib().stcn_pool_release(), "stcn_pool_release")
 
 
-def _model_for(prop_net, fuse_net, device_index: int) -> _Model:
+def _top_k_of(prop_net) -> int:
+    """The ``top_k`` a core built on ``prop_net`` reads with: ``prop_net.top_k`` (this package's weight container), else
+    ``prop_net.memory.top_k`` (a live reference module: prop_net.py:149 hands it to EvalMemoryReader), else the reference's default 50."""
+    if hasattr(prop_net, "top_k"):
+        top_k = prop_net.top_k
+    elif hasattr(getattr(prop_net, "memory", None), "top_k"):
+        top_k = prop_net.memory.top_k
+    else:
+        top_k = 50
+    return check_top_k(top_k)
+
+
+def _model_for(prop_net, fuse_net, device_index: int, top_k: int = 50) -> _Model:
     """The engine works on a BN-folded, repacked SNAPSHOT of the weights.  The reference reads the live parameters, so the
     snapshot is keyed on a fingerprint of both modules' tensors: loading another checkpoint into the same module objects
     (one script evaluating several checkpoints) yields a fresh model.  A small LRU per (prop_net, device) keeps the last
     few snapshots, so alternating two fusion networks (or fuse_net / None) does not re-upload 218 MB per construction;
-    older ones die with their last engine."""
-    key = (device_index, _fingerprint(prop_net), _fingerprint(fuse_net))      # outside the lock: it may sync the device
+    older ones die with their last engine.  ``top_k`` is part of the model (it changes results) and of the key: the same module
+    read with another ``top_k`` (the attribute was changed between two cores) is another model."""
+    key = (device_index, _fingerprint(prop_net), _fingerprint(fuse_net), int(top_k))      # outside the lock: it may sync the device
     with _MODEL_LOCK:                       # engines may be created from several host threads (one per video)
         per_net = _MODEL_CACHE.setdefault(prop_net, {})
         hit = per_net.get(key)
@@ -182,7 +197,7 @@ def _model_for(prop_net, fuse_net, device_index: int) -> _Model:
         mine = [k for k in per_net if k[0] == device_index]
         for k in mine[:max(0, len(mine) - (_SNAPSHOTS_PER_DEVICE - 1))]:     # least recently used first
             del per_net[k]
-        model = _Model(prop_net, fuse_net, device_index)
+        model = _Model(prop_net, fuse_net, device_index, top_k)
         per_net[key] = (model, weakref.ref(fuse_net) if fuse_net is not None else None)
         return model
 
@@ -220,7 +235,7 @@ class InferenceCore:
         self.nh, self.nw = self.h + lh + uh, self.w + lw + uw
         self.kh, self.kw = self.nh // 16, self.nw // 16
         t_0 = time.perf_counter()
-        self._model = _model_for(prop_net, fuse_net, self.device.index or 0)
+        self._model = _model_for(prop_net, fuse_net, self.device.index or 0, _top_k_of(prop_net))
         t_1 = time.perf_counter()
         with torch.cuda.device(self.device):
             self._stream = torch.cuda.current_stream()
@@ -342,6 +357,13 @@ class InferenceCore:
     def images(self):
         lw, uw, lh, uh = self.pad
         return torch.nn.functional.pad(self._images_unpadded, (lw, uw, lh, uh))
+
+    @property
+    def top_k(self) -> int:
+        """Rows of the memory bank each query reads (``PropagationNetwork(top_k=...)``), as the engine's model holds it."""
+        v = C.c_int32()
+        _lib.check(_lib.lib().stcn_model_get_top_k(self._model.handle, C.byref(v)), "stcn_model_get_top_k")
+        return int(v.value)
 
     def stats(self) -> dict:
         s = _lib.Stats()

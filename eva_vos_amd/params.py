@@ -18,6 +18,8 @@ hand-written module classes.
 """
 from __future__ import annotations
 
+import numbers
+
 import torch.nn as nn
 
 
@@ -113,16 +115,30 @@ def _decoder():
                 pred=_conv(256, 1, 3))
 
 
+MAX_TOP_K = 50      # STCN_MAX_TOP_K of include/stcn_hip.h: every capacity of the HIP memory read is sized for it
+
+
+def check_top_k(top_k) -> int:
+    """``top_k`` as the HIP memory read takes it: an int in 1..50 (reference prop_net.py:141; softmax_w_top, prop_net.py:53-60)."""
+    if top_k is None:
+        raise ValueError("top_k=None (the dense softmax over the whole memory bank) is not built: the HIP memory read "
+                         f"supports an integer top_k in 1..{MAX_TOP_K}")
+    if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or not 1 <= int(top_k) <= MAX_TOP_K:
+        raise ValueError(f"top_k={top_k!r}: the HIP memory read supports an integer top_k in 1..{MAX_TOP_K} "
+                         "(reference prop_net.py:141)")
+    return int(top_k)
+
+
 class PropagationNetwork(_Bag):
-    """Weights of the STCN propagation network (see module docstring)."""
+    """Weights of the STCN propagation network (see module docstring).  ``top_k`` (1..50, default 50): the rows of the memory bank each
+    query reads; a hyper-parameter of the model, not a weight - it is no ``state_dict`` entry."""
 
     def __init__(self, top_k=50):
+        top_k = check_top_k(top_k)
         super().__init__(value_encoder=_value_encoder(), key_encoder=_key_encoder(),
                          key_proj=_Bag(key_proj=_conv(1024, 64, 3)),
                          key_comp=_conv(1024, 512, 3),
                          decoder=_decoder())
-        if top_k != 50:
-            raise ValueError("the HIP memory reader is built for top_k=50 (reference prop_net.py:141)")
         self.top_k = top_k
 
 

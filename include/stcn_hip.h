@@ -64,6 +64,22 @@ int stcn_model_create(int device,
                       stcn_model **out);
 int stcn_model_destroy(stcn_model *m);
 
+/* Model hyper-parameters that CHANGE RESULTS (unlike stcn_engine_opts below).  A NON-POSITIVE field means "not given".
+ *   top_k   rows of the memory bank each query reads: softmax over the top_k best affinities, 1 .. STCN_MAX_TOP_K, default 50
+ *           (`top_k` of PropagationNetwork.__init__, model/propagation/prop_net.py:141, handed to MemoryReader and applied by
+ *           softmax_w_top, prop_net.py:53-60).  Every capacity of the read is sized for 50; a larger value, and the reference's
+ *           top_k=None (a dense softmax over the whole bank, another kernel family), return STCN_E_INVALID / are not expressible.
+ * stcn_model_create(...) = stcn_model_create_ex(..., NULL, out).  Arguments are validated before the first device call.  Engines,
+ * their clones and resets read the value from the model they share. */
+#define STCN_MAX_TOP_K  50
+typedef struct { int32_t top_k; } stcn_model_opts;
+int stcn_model_create_ex(int device,
+                         const stcn_weight_desc *prop, int n_prop,
+                         const stcn_weight_desc *fuse, int n_fuse,
+                         const stcn_model_opts *opts, stcn_model **out);
+/* The top_k the model runs with (PropagationNetwork.memory.top_k, prop_net.py:149). */
+int stcn_model_get_top_k(const stcn_model *m, int32_t *top_k);
+
 /* Create the per-video engine.
  *   images_dev : fp32 [1,T,3,H,W] (NCHW, normalized, unpadded), read once during this call.
  *   prob_dev   : fp32 [k+1,T,1,nh,nw] owned by the caller (a torch tensor in the shim); the engine
@@ -181,12 +197,19 @@ int stcn_test_encode_value(const stcn_model *m, void *stream, const float *img, 
  * mk [N,64], mv [k,N,512], qk [Q,64] -> topk_idx [Q,50] (int32), topk_w [Q,50], readout [k,Q,512]. */
 int stcn_test_memory_read(void *stream, const float *mk, const float *mv, const float *qk,
                           int N, int Q, int k, int32_t *topk_idx, float *topk_w, float *readout);
+/* The same read with the cut given (softmax_w_top(x, top=top_k), prop_net.py:53-60): 1 <= top_k <= STCN_MAX_TOP_K, N >= top_k;
+ * topk_idx / topk_w are [Q,top_k].  stcn_test_memory_read(...) is the top_k = 50 case. */
+int stcn_test_memory_read_k(void *stream, const float *mk, const float *mv, const float *qk,
+                            int N, int Q, int k, int top_k, int32_t *topk_idx, float *topk_w, float *readout);
 
 /* Measurement hook of the same read: `iters` whole reads on caller-provided device data between two HIP events on
  * `stream` (scratch allocated outside the timed region); *ms = average per read; plan7 (may be NULL) receives the launch
  * plan {steps, pass-1 sample stride, sampled steps, pass-1 chunks, steps per chunk, pass-2 chunks, steps per chunk}. */
 int stcn_bench_memory_read(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k,
                            int iters, float *readout, float *ms, int32_t *plan7);
+/* ... at another cut (prop_net.py:53-60 with top = top_k; same limits as stcn_test_memory_read_k); the call above is top_k = 50. */
+int stcn_bench_memory_read_k(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k,
+                             int iters, float *readout, float *ms, int32_t *plan7);
 
 /* Decoder + sigmoid + soft aggregation (prop_net.py:13-30,189-192; aggregate.py:22-37).
  * readout [k,hw16,512], f16_thin/f8/f4 NHWC -> logit4 [k,hw4] (may be NULL), agg [k+1,nh*nw]. */
@@ -204,7 +227,8 @@ int stcn_test_fusion(const stcn_model *m, void *stream, const float *img, const 
                      const float *curr, const float *attn, float nc, float nr, int nh, int nw,
                      float *logit);
 
-/* Launch plan of the top-50 memory read for N bank rows and Q queries (what stcn_test_memory_read / the engine will run):
+/* Launch plan of the top-k memory read for N bank rows and Q queries (what stcn_test_memory_read[_k] / the engine will run; it does
+ * not depend on top_k):
  * plan7 = { 64-row steps, pass-1 sample stride, sampled steps, pass-1 chunks, steps per pass-1 chunk, pass-2 chunks,
  * steps per pass-2 chunk }.  Lets tests assert WHICH plan (sample stride 1/2/4/8) a comparison exercised. */
 int stcn_memread_plan(int N, int Q, int32_t *plan7);
