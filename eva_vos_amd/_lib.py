@@ -28,8 +28,8 @@ class EngineOpts(C.Structure):
 
 
 class ModelOpts(C.Structure):
-    """stcn_model_opts: a non-positive field = not given (top_k: 50)."""
-    _fields_ = [("top_k", C.c_int32)]
+    """stcn_model_opts: a non-positive field = not given (top_k: 50; km: the plain read)."""
+    _fields_ = [("top_k", C.c_int32), ("km", C.c_float)]
 
 
 class Stats(C.Structure):
@@ -44,6 +44,7 @@ PROTOTYPES = {
     "stcn_model_create": (_I, [_I, C.POINTER(WeightDesc), _I, C.POINTER(WeightDesc), _I, C.POINTER(_P)]),
     "stcn_model_create_ex": (_I, [_I, C.POINTER(WeightDesc), _I, C.POINTER(WeightDesc), _I, C.POINTER(ModelOpts), C.POINTER(_P)]),
     "stcn_model_get_top_k": (_I, [_P, C.POINTER(C.c_int32)]),
+    "stcn_model_get_km": (_I, [_P, C.POINTER(C.c_float)]),
     "stcn_model_destroy": (_I, [_P]),
     "stcn_engine_create": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(_P)]),
     "stcn_engine_create_ex": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(EngineOpts), C.POINTER(_P)]),
@@ -65,8 +66,10 @@ PROTOTYPES = {
     "stcn_test_encode_value": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "stcn_test_memory_read": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "stcn_test_memory_read_k": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "stcn_test_memory_read_km": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "stcn_bench_memory_read": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, C.POINTER(_F), C.POINTER(C.c_int32)]),
     "stcn_bench_memory_read_k": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, C.POINTER(_F), C.POINTER(C.c_int32)]),
+    "stcn_bench_memory_read_km": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, C.POINTER(_F), C.POINTER(C.c_int32)]),
     "stcn_memread_plan": (_I, [_I, _I, C.POINTER(C.c_int32)]),
     "stcn_test_fail_at": (_I, [_I]),
     "stcn_test_side_delay_us": (_I, [_I]),

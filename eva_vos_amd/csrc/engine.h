@@ -53,6 +53,7 @@ struct Model {
     CbamW cbam{};
     bool has_fuse = false;
     int top_k = MEMREAD_MAX_TOPK;          // rows per query of the memory read (PropagationNetwork(top_k=...), prop_net.py:141)
+    float km = 0.f;                        // > 0: the kernelized read, standard deviation of its Gaussian (EvalMemoryReader(top_k, km), prop_net.py:75-99); 0: the plain read
     int wino4_min_wg = 100;                // fewest 32 x 32 workgroups for which a flagged layer takes the F(4x4) kernel (tests: 0)
     std::vector<void *> allocs;
     const ConvW &c(const std::string &name) const;
@@ -110,6 +111,7 @@ struct Work {
     float *pooled = nullptr, *amap = nullptr, *attn = nullptr;   // attention read
     float *cand_v = nullptr; int32_t *cand_i = nullptr, *cand_n = nullptr;   // memory-read chunk winners
     float *gmax = nullptr, *tau = nullptr;                       // memory-read group maxima / thresholds
+    int32_t *centre = nullptr;          // kernelized read: [group][memread_centre_stride(bank rows)] row centres; grows with the bank (bank_reserve), not in allocs
     float *qk = nullptr;                // [group][hw16][64] queries of a decode group
     float *vin = nullptr;               // value-encoder packed input [k][npix][8]
     Prof *prof = nullptr;
@@ -204,6 +206,7 @@ struct stcn_engine {
     // memory bank: rows = slots * hw16
     int bank_cap = 0, n_certain = 0;
     float *bank_k = nullptr, *bank_msq = nullptr, *bank_v = nullptr;
+    int32_t *bank_centre = nullptr;    // kernelized read (model km > 0): the row-centre scratch of work / work2, one block each, sized for bank_cap
     std::vector<void *> retired;       // bank buffers replaced by a larger generation, freed once retire_ev has fired
     hipEvent_t retire_ev = nullptr;
     std::set<int> interacted;

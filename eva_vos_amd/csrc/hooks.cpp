@@ -239,19 +239,47 @@ int stcn_test_memory_read(void *stream, const float *mk, const float *mv, const 
 
 int stcn_test_memory_read_k(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k,
                             int32_t *topk_idx, float *topk_w, float *readout) {
+    return stcn_test_memory_read_km(stream, mk, mv, qk, N, Q, k, top_k, 0, 0, 0.f, nullptr, topk_idx, topk_w, readout);
+}
+
+// the kernelized read's arguments of the two hooks below: km > 0 finite, the Q queries whole frames of h16 x w16 positions (16-bit coordinates)
+static bool km_args_ok(int Q, int h16, int w16, float km) {
+    return std::isfinite(km) && km > 0.f && h16 >= 1 && w16 >= 1 && h16 < 32768 && w16 < 32768 && (long)h16 * w16 <= Q && Q % (h16 * w16) == 0;
+}
+// scratch of the kernelized read for the hooks: |qk|^2 per query and the packed row centres
+struct KmScratch {
+    DevBuf qsq, cen;
+    MemReadKm km{};
+    int init(const float *qk, int N, int Q, int h16, int w16, float sigma, int32_t *centres, hipStream_t s) {
+        RC(qsq.alloc(Q)); RC(cen.alloc((size_t)(Q / (h16 * w16)) * memread_centre_stride(N)));
+        rowsumsq_launch(qk, Q, 64, qsq.p, s);
+        km = MemReadKm{sigma, h16, w16, qsq.p, (long)h16 * w16, reinterpret_cast<int32_t *>(cen.p), centres};
+        return STCN_OK;
+    }
+};
+
+int stcn_test_memory_read_km(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k, int h16, int w16,
+                             float km, int32_t *centres, int32_t *topk_idx, float *topk_w, float *readout) {
+    const bool with_km = h16 != 0 || w16 != 0 || km != 0.f || centres;       // all zero: the plain read (stcn_test_memory_read_k)
     if (!mk || !mv || !qk || !readout || top_k < 1 || top_k > STCN_MAX_TOP_K || N < top_k || Q < 1 || k < 1) {
         set_error("stcn_test_memory_read: bad arguments (1 <= top_k <= %d, N >= top_k; top_k=%d N=%d)", STCN_MAX_TOP_K, top_k, N);
         return STCN_E_INVALID;
     }
+    if (with_km && !km_args_ok(Q, h16, w16, km)) {
+        set_error("stcn_test_memory_read_km: bad arguments (km > 0 finite, Q a multiple of h16 * w16; km=%f h16=%d w16=%d Q=%d)", (double)km, h16, w16, Q);
+        return STCN_E_INVALID;
+    }
     hipStream_t s = (hipStream_t)stream;
     DevBuf msq, cv, ci, cn, gm, tau;
+    KmScratch ks;
     const size_t pairs = memread_list_pairs(Q);
     RC(msq.alloc(N + 64)); RC(cv.alloc(pairs * MEMREAD_MAX_TOPK)); RC(ci.alloc(pairs * MEMREAD_MAX_TOPK)); RC(cn.alloc(pairs));
     RC(gm.alloc(pairs * 64)); RC(tau.alloc(Q));
+    if (with_km) RC(ks.init(qk, N, Q, h16, w16, km, centres, s));
     HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(N + 64) * 4, s));
     rowsumsq_launch(mk, N, 64, msq.p, s);
     memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, topk_idx, topk_w,
-                       MemReadScratch{cv.p, reinterpret_cast<int32_t *>(ci.p), reinterpret_cast<int32_t *>(cn.p), gm.p, tau.p}, s);
+                       MemReadScratch{cv.p, reinterpret_cast<int32_t *>(ci.p), reinterpret_cast<int32_t *>(cn.p), gm.p, tau.p}, s, with_km ? &ks.km : nullptr);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     return STCN_OK;
@@ -266,25 +294,38 @@ int stcn_bench_memory_read(void *stream, const float *mk, const float *mv, const
 
 int stcn_bench_memory_read_k(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k, int iters,
                              float *readout, float *ms, int32_t *plan7) {
+    return stcn_bench_memory_read_km(stream, mk, mv, qk, N, Q, k, top_k, 0, 0, 0.f, iters, readout, ms, plan7);
+}
+
+int stcn_bench_memory_read_km(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k, int h16, int w16,
+                              float km, int iters, float *readout, float *ms, int32_t *plan7) {
+    const bool with_km = h16 != 0 || w16 != 0 || km != 0.f;                    // all zero: the plain read (stcn_bench_memory_read_k)
     if (!mk || !mv || !qk || !readout || !ms || top_k < 1 || top_k > STCN_MAX_TOP_K || N < top_k || Q < 1 || k < 1 || iters < 1) {
         set_error("stcn_bench_memory_read: bad arguments (1 <= top_k <= %d, N >= top_k; top_k=%d N=%d)", STCN_MAX_TOP_K, top_k, N);
         return STCN_E_INVALID;
     }
+    if (with_km && !km_args_ok(Q, h16, w16, km)) {
+        set_error("stcn_bench_memory_read_km: bad arguments (km > 0 finite, Q a multiple of h16 * w16; km=%f h16=%d w16=%d Q=%d)", (double)km, h16, w16, Q);
+        return STCN_E_INVALID;
+    }
     hipStream_t s = (hipStream_t)stream;
     DevBuf msq, cv, ci, cn, gm, tau;
+    KmScratch ks;
     const size_t pairs = memread_list_pairs(Q);
     RC(msq.alloc(N + 64)); RC(cv.alloc(pairs * MEMREAD_MAX_TOPK)); RC(ci.alloc(pairs * MEMREAD_MAX_TOPK)); RC(cn.alloc(pairs));
     RC(gm.alloc(pairs * 64)); RC(tau.alloc(Q));
+    if (with_km) RC(ks.init(qk, N, Q, h16, w16, km, nullptr, s));
+    const MemReadKm *kmo = with_km ? &ks.km : nullptr;
     HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(N + 64) * 4, s));
     rowsumsq_launch(mk, N, 64, msq.p, s);
     const MemReadScratch scr{cv.p, reinterpret_cast<int32_t *>(ci.p), reinterpret_cast<int32_t *>(cn.p), gm.p, tau.p};
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     for (int it = 0; it < 2; ++it)
-        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, nullptr, nullptr, scr, s);
+        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, nullptr, nullptr, scr, s, kmo);
     HIPCHK(hipEventRecord(e0, s));
     for (int it = 0; it < iters; ++it)
-        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, nullptr, nullptr, scr, s);
+        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, nullptr, nullptr, scr, s, kmo);
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipEventSynchronize(e1));
     HIPCHK(hipEventElapsedTime(ms, e0, e1));

@@ -237,11 +237,18 @@ static inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_
     else hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
 }
 #endif
+// The kernelized read (EvalMemoryReader(top_k, km), prop_net.py:92-99): a Gaussian of standard deviation `sigma` around the query each bank row
+// matches best weights the affinity before the cut.  The Q queries are Q / (h16 * w16) whole frames of h16 x w16 positions; qsq: |qk|^2 of frame
+// f at qsq + f * qsq_fs; centre: scratch of (Q / (h16 * w16)) * memread_centre_stride(N) int32; centre_idx (may be null): [frames][N], the
+// best query of every row within each frame
+struct MemReadKm { float sigma; int h16, w16; const float *qsq; long qsq_fs; int32_t *centre; int32_t *centre_idx; };
+long memread_centre_stride(int N);
 // mk [N,64], msq [N] (+ >= 64 readable floats of padding), qk [Q,64]; mv [k][N][512] with object stride mv_os; readout [k][Q][512] with
 // object stride ro_os.  top_k: 1 .. MEMREAD_MAX_TOPK rows per query, N >= top_k.  topk_idx/topk_w optional outputs [Q,top_k].
+// km == nullptr: the plain read, the kernels it always ran.
 void memory_read_launch(const float *mk, const float *msq, const float *qk, int N, int Q,
                         const float *mv, long mv_os, int k, int top_k, float *readout, long ro_os,
-                        int32_t *topk_idx, float *topk_w, MemReadScratch scr, hipStream_t s);
+                        int32_t *topk_idx, float *topk_w, MemReadScratch scr, hipStream_t s, const MemReadKm *km = nullptr);
 // fusion attention read: mk,qk [hw,64]; pos,neg [kk][16h*16w planes] -> attn [kk][2][nh*nw]; pooled: scratch of attention_nchp(2 kk) * h * w floats
 struct AttnScratch { float *gmax, *cmax, *part; };   // [256][hw], [hw], attention_part_floats(kk, hw) ([16][hw][19] up to 8 objects)
 int attention_nchp(int nch);                          // channels 2 kk padded to the widths the pass kernel is instantiated for

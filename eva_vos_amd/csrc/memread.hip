@@ -23,6 +23,14 @@
 //   the read and the headline are the same within the repeats of one box), so there is ONE instantiation.  Every capacity is sized for 50 and
 //   does not move: candidate lists keep a stride of 50, CAP2 = 64 stays above the cut, merge_readout stages MAXCHUNK2 * 50 entries, one lane
 //   per selected row.  top_k = None of the reference (a dense softmax over the whole bank) is another kernel family and is not built.
+// km (the kernelized read, EvalMemoryReader(top_k, km), prop_net.py:33-51,92-99): every memory row n takes the query it matches best in the
+//   frame being read, (cy_n, cx_n), and its affinities to that frame are weighted by a Gaussian of standard deviation km around that
+//   position BEFORE the cut: exp(S - max) * g.  In the log domain that is an additive bias on the score,
+//     B[n,q] = S[n,q] - ((y_q - cy_n)^2 + (x_q - cx_n)^2) / (2 km^2),
+//   and exp(S - max) * g is monotone in B: selection, near-tie re-score, softmax and gather are the plain read's, applied to B.
+//   row_centre_kernel finds the centres (one more affinity walk, roles of keys and queries swapped, per frame of a decode group);
+//   the KM instantiations of affinity_tile_kernel / merge_readout_kernel add the bias in the tile epilogue / to the fp64 re-score.
+//   Without km the launch path runs the instantiations it always ran.
 #include <cstdlib>
 #include <type_traits>
 
@@ -31,6 +39,17 @@
 namespace stcn {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+
+// device side of the kernelized read: centre [frames][cstride] holds (cy << 16 | cx) of every bank row for every frame of the queries,
+// frame f owning the queries [f * hw16, (f + 1) * hw16); inv2s = 1 / (2 km^2)
+struct KmArgs { const int32_t *centre; long cstride; int hw16, w16; float inv2s; };
+// squared distance of the packed positions a, b = (x, y) as 16-bit halves: one packed subtract, one dot product
+__device__ __forceinline__ int km_dist2(s16x2 a, int b) {
+    const s16x2 d = a - __builtin_bit_cast(s16x2, b);
+    return __builtin_amdgcn_sdot2(d, d, 0, false);
+}
 
 static constexpr int TOPK = MEMREAD_MAX_TOPK;   // the largest cut, the default model's, and the stride of every candidate list
 static constexpr int CAP = 128;       // per-(query, chunk) candidate list capacity (>= TOPK + 64)
@@ -145,11 +164,16 @@ static constexpr int LISTS_PER_WAVE = 2 * 16 * CAP2 + 32;               // LV, L
 static constexpr int NGRP2 = 64;                                        // pass-1 maxima per query per chunk
 
 //   K: the cut of pass 2 (1 .. TOPK, wave-uniform).  Pass 1 does not depend on it.
-template <bool COLLECT, bool SINGLE = false>
+//   KM: both passes work on the biased score B = S - d^2 / (2 km^2) (in the kernel's units: U - 4 d^2 / (2 km^2)), d = distance of the lane's
+//     query position from the row's centre in the query's frame.  The lane's packed position and frame are resident; a step's 16 centres per
+//     lane (4 loads of 16 bytes, the same address for the 16 lanes of a lane group within one frame) are requested with the step's first
+//     fragments and used in the epilogue: subtract, dot product, convert, fma per score - nothing in the MFMA loop.  Both passes evaluate the
+//     same expression on the same accumulator, so pass 1's bound holds for what pass 2 sees.
+template <bool COLLECT, bool SINGLE = false, bool KM = false>
 __global__ __launch_bounds__(256, SINGLE ? 3 : 2) void affinity_tile_kernel(
     const float *__restrict__ mk, const float *__restrict__ msq, const float *__restrict__ qk, int N, int Q, int ns,
     int ss, int spc, float *__restrict__ gmax, const float *__restrict__ tau_in, float *__restrict__ cand_v,
-    int32_t *__restrict__ cand_i, int32_t *__restrict__ cand_n, const int K) {
+    int32_t *__restrict__ cand_i, int32_t *__restrict__ cand_n, const int K, const KmArgs km) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     constexpr int NBUF = SINGLE ? 1 : 2;                                // SINGLE: one key tile buffer, two barriers per step, 3 workgroups per CU
@@ -167,6 +191,15 @@ __global__ __launch_bounds__(256, SINGLE ? 3 : 2) void affinity_tile_kernel(
 
     f32x4 bq[4];
     load_bq(qk, Q, min(q0, Q - 1), lane, bq);
+    s16x2 pq = {0, 0};                                                  // KM: the lane's query position (x, y) in its frame
+    const int32_t *cl = nullptr;                                        // KM: centres of the lane's frame, at the lane's first C row
+    float nkb = 0.f;
+    if constexpr (KM) {
+        const int fq = qcol / km.hw16, p = qcol - fq * km.hw16, y = p / km.w16;
+        pq = s16x2{(short)(p - y * km.w16), (short)y};
+        cl = km.centre + (long)fq * km.cstride + 4 * g;
+        nkb = -4.f * km.inv2s;
+    }
     // the kernel works on U = mk.qk - |mk|^2/2 = 4 S (S = the reference's affinity up to the per-query constant): maxima
     // and thresholds are compared unscaled, a score is multiplied by 1/4 (exact) when it leaves the kernel
     float tcol = -__builtin_inff();
@@ -225,6 +258,11 @@ __global__ __launch_bounds__(256, SINGLE ? 3 : 2) void affinity_tile_kernel(
             fa[0][rb] = *reinterpret_cast<const f32x4 *>(kt + a_off[0] + rb * 1024);
             acc[rb] = *reinterpret_cast<const f32x4 *>(kt + m_off + rb * 16);
         }
+        i32x4 cen[4];
+        if constexpr (KM) {                                              // rows up to the end of the last step are inside the (padded) centre rows
+#pragma unroll
+            for (int rb = 0; rb < 4; ++rb) cen[rb] = *reinterpret_cast<const i32x4 *>(cl + row0 + rb * 16);
+        }
         __builtin_amdgcn_sched_barrier(0);
         // tile j+1 (loaded a step ago) -> the buffer whose readers finished before the previous barrier; tile j+2 -> registers
         // (unconditional: past the chunk they move zeros / an unused tile)
@@ -248,6 +286,12 @@ __global__ __launch_bounds__(256, SINGLE ? 3 : 2) void affinity_tile_kernel(
                 for (int rb = 0; rb < 4; ++rb)
                     acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[cur][rb][e], bq[kb][e], acc[rb], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (KM) {
+#pragma unroll
+            for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[rb][e] = __builtin_fmaf(nkb, (float)km_dist2(pq, cen[rb][e]), acc[rb][e]);
         }
         if (row0 + HROWS > N) {                                          // ragged last step: rows beyond the bank never win
 #pragma unroll
@@ -394,6 +438,74 @@ __global__ __launch_bounds__(64 * WAVES) void colmax_pass_kernel(
     }
 }
 
+// Centres of the kernelized read: centre[f][n] = the query of frame f that bank row n matches best,
+//   argmax over the frame's hw16 queries q of (mk[n] . qk[q] - |qk[q]|^2 / 2)
+// (prop_net.py:94: affinity.max(2)[1]; the row-constant -|mk[n]|^2 drops out, the -|qk|^2 term does not: this argmax runs along a row), ties to
+// the lowest query.  The tile walk of colmax_pass_kernel with the roles swapped: a wave keeps 16 * NB bank rows resident as B fragments and walks
+// the frame's queries in 64-row steps as A fragments straight from global / L2, -|qk|^2 / 2 as the initial accumulator; every lane keeps a running
+// (max, query) over the queries of its C rows - visited in rising order, so a strict compare keeps the lowest - and the four lane groups of a
+// column combine at the end.  Written as (cy << 16 | cx) for the bias of the passes, and as the query index when centre_idx is given (tests).
+template <int WAVES, int NB>
+__global__ __launch_bounds__(64 * WAVES) void row_centre_kernel(
+    const float *__restrict__ mk, int N, const float *__restrict__ qk, const float *__restrict__ qsq, long qsq_fs, int hw16, int w16,
+    int32_t *__restrict__ centre, long cstride, int32_t *__restrict__ centre_idx) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n0 = (blockIdx.x * WAVES + wave) * 16 * NB;
+    if (n0 >= N) return;
+    const int f = blockIdx.y;
+    const float *qf = qk + (long)f * hw16 * 64, *sf = qsq + (long)f * qsq_fs;
+    const int g = lane >> 4, col = lane & 15;
+    f32x4 bm[NB][4];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) load_bq(mk, N, min(n0 + 16 * b, N - 1), lane, bm[b]);
+    float best[NB];
+    int bi[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) { best[b] = -__builtin_inff(); bi[b] = 0; }
+    for (int row0 = 0; row0 < hw16; row0 += HROWS) {
+        HalfFrag cur;
+#pragma unroll
+        for (int rb = 0; rb < 4; ++rb) {
+            const float *ap = qf + (long)min(row0 + rb * 16 + col, hw16 - 1) * 64 + 4 * g;
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) cur.a[rb][kb] = *reinterpret_cast<const f32x4 *>(ap + 16 * kb);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cur.c[rb][j] = sf[min(row0 + rb * 16 + 4 * g + j, hw16 - 1)];
+        }
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            f32x4 acc[4];
+            mfma_half(cur, bm[b], acc);                                  // (qk[q] . mk[n] - |qk[q]|^2 / 2) / 4, q = row0 + 16 rb + 4 g + j, n = n0 + 16 b + col
+#pragma unroll
+            for (int rb = 0; rb < 4; ++rb)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int q = row0 + rb * 16 + 4 * g + j;
+                    const bool take = q < hw16 && acc[rb][j] > best[b];
+                    best[b] = take ? acc[rb][j] : best[b];
+                    bi[b] = take ? q : bi[b];
+                }
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int o = 16; o <= 32; o <<= 1) {
+            const float ov = __shfl_xor(best[b], o);
+            const int oi = __shfl_xor(bi[b], o);
+            const bool take = ov > best[b] || (ov == best[b] && oi < bi[b]);
+            best[b] = take ? ov : best[b];
+            bi[b] = take ? oi : bi[b];
+        }
+        const int n = n0 + 16 * b + col;
+        if (g == 0 && n < N) {
+            const int cy = bi[b] / w16;
+            centre[(long)f * cstride + n] = (cy << 16) | (bi[b] - cy * w16);
+            if (centre_idx) centre_idx[(long)f * N + n] = bi[b];
+        }
+    }
+}
+
 // tau[q] = K-th largest of the G group maxima of query q (-inf when fewer than K are finite); G <= 512
 __global__ __launch_bounds__(256) void threshold_kernel(const float *__restrict__ gmax, int G, int Q,
                                                         float *__restrict__ tau, const int K) {
@@ -441,13 +553,16 @@ __device__ __forceinline__ double shfl_f64(double v, int src) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 
+// KM: the candidates carry biased scores; the fp64 re-score adds the same bias (the row's centre in the query's frame) to the exact affinity
+template <bool KM = false>
 __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restrict__ cand_v,
                                                             const int32_t *__restrict__ cand_i,
                                                             const int32_t *__restrict__ cand_n, int NC, int Q,
                                                             const float *__restrict__ mv, long mv_os, int k,
                                                             float *__restrict__ readout, long ro_os,
                                                             int32_t *__restrict__ topk_idx, float *__restrict__ topk_w,
-                                                            const float *__restrict__ mk, const float *__restrict__ qk, const int K) {
+                                                            const float *__restrict__ mk, const float *__restrict__ qk, const int K,
+                                                            const KmArgs km) {
     __shared__ float s_v[4][MAXCHUNK2 * TOPK];
     __shared__ int s_i[4][MAXCHUNK2 * TOPK];
     __shared__ float s_w[4][64];
@@ -515,6 +630,10 @@ __global__ __launch_bounds__(256) void merge_readout_kernel(const float *__restr
                     for (int u = 0; u < 4; ++u) { dot += (double)a[u] * (double)b[u]; sq += (double)a[u] * (double)a[u]; }
                 }
                 d = (dot - 0.5 * sq) * 0.25;
+                if constexpr (KM) {
+                    const int fq = q / km.hw16, p = q - fq * km.hw16, y = p / km.w16;
+                    d -= (double)km.inv2s * (double)km_dist2(s16x2{(short)(p - y * km.w16), (short)y}, km.centre[(long)fq * km.cstride + row]);
+                }
             }
             int rank = 0;
             for (int j = 0; j < nnear; ++j) {
@@ -662,39 +781,52 @@ MemReadPlan memread_plan(int N, int Q) {
 // bound of nc * Q over both passes: nc1 <= min(8, 1024 / qblocks) and nc2 <= max(1, 512 / qblocks) with Q <= 64 qblocks
 size_t memread_list_pairs(int Q) { return (size_t)65536 + (size_t)Q + 64; }
 
+long memread_centre_stride(int N) { return (long)((N + HROWS - 1) / HROWS) * HROWS; }
+
 void memory_read_launch(const float *mk, const float *msq, const float *qk, int N, int Q, const float *mv,
                         long mv_os, int k, int top_k, float *readout, long ro_os, int32_t *topk_idx, float *topk_w,
-                        MemReadScratch scr, hipStream_t s) {
+                        MemReadScratch scr, hipStream_t s, const MemReadKm *kmo) {
     const MemReadPlan pl = memread_plan(N, Q);
     const int qblocks = (Q + 63) / 64;
     static const bool rescore = [] { const char *e = getenv("STCN_MEMREAD_RESCORE"); return !e || atoi(e) != 0; }();      // measurement aid: 0 = plain fp32 cut
     const size_t lds1 = (size_t)2 * KT_FLOATS * sizeof(float);
     const bool single = memread_single_buffer();
     const size_t lds2 = (single ? lds1 / 2 : lds1) + (size_t)4 * LISTS_PER_WAVE * sizeof(float);
-    allow_big_lds(reinterpret_cast<const void *>(&affinity_tile_kernel<true, true>), lds2);
-    hipLaunchKernelGGL((affinity_tile_kernel<false>), dim3(qblocks, pl.nc1), dim3(256), lds1, s, mk, msq, qk, N, Q, pl.ns, pl.ss,
-                       pl.spc1, scr.gmax, (const float *)nullptr, (float *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, top_k);
-    hipLaunchKernelGGL(threshold_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.gmax, pl.nc1 * NGRP2, Q, scr.tau, top_k);
-    hipLaunchKernelGGL((affinity_tile_kernel<true, true>), dim3(qblocks, pl.nc2), dim3(256), lds2, s, mk, msq, qk, N, Q, pl.steps, 1,
-                       pl.spc2, (float *)nullptr, scr.tau, scr.cand_v, scr.cand_i, scr.cand_n, top_k);
-    if (k == 1 || topk_idx || topk_w) {
-        hipLaunchKernelGGL(merge_readout_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.cand_v, scr.cand_i, scr.cand_n, pl.nc2, Q,
-                           mv, mv_os, k, readout, ro_os, topk_idx, topk_w, rescore ? mk : nullptr, qk, top_k);
-        return;
-    }
     // several objects: merge once per query (indices / weights [Q][top_k] into the group-maxima scratch, free since threshold_kernel),
     // then gather with one wave per (query, object)
-    int32_t *gi = reinterpret_cast<int32_t *>(scr.gmax);
-    float *gw = scr.gmax + (size_t)Q * TOPK;
-    hipLaunchKernelGGL(merge_readout_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.cand_v, scr.cand_i, scr.cand_n, pl.nc2, Q,
-                       mv, mv_os, 0, readout, ro_os, gi, gw, rescore ? mk : nullptr, qk, top_k);
-    hipLaunchKernelGGL(gather_readout_kernel, dim3((Q + 3) / 4, k), dim3(256), 0, s, gi, gw, Q, mv, mv_os, readout, ro_os, top_k);
+    const bool split = !(k == 1 || topk_idx || topk_w);
+    int32_t *gi = split ? reinterpret_cast<int32_t *>(scr.gmax) : topk_idx;
+    float *gw = split ? scr.gmax + (size_t)Q * TOPK : topk_w;
+    const KmArgs km = kmo ? KmArgs{kmo->centre, memread_centre_stride(N), kmo->h16 * kmo->w16, kmo->w16, 1.f / (2.f * kmo->sigma * kmo->sigma)} : KmArgs{};
+    if (kmo) {   // the kernelized read: centres of every bank row per query frame, then the same sequence on the biased score
+        constexpr int CW = 4, CB = 2;
+        hipLaunchKernelGGL((row_centre_kernel<CW, CB>), dim3((N + 16 * CB * CW - 1) / (16 * CB * CW), Q / km.hw16), dim3(64 * CW), 0, s, mk, N, qk, kmo->qsq,
+                           kmo->qsq_fs, km.hw16, km.w16, kmo->centre, km.cstride, kmo->centre_idx);
+        allow_big_lds(reinterpret_cast<const void *>(&affinity_tile_kernel<true, true, true>), lds2);
+        hipLaunchKernelGGL((affinity_tile_kernel<false, false, true>), dim3(qblocks, pl.nc1), dim3(256), lds1, s, mk, msq, qk, N, Q, pl.ns, pl.ss,
+                           pl.spc1, scr.gmax, (const float *)nullptr, (float *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, top_k, km);
+        hipLaunchKernelGGL(threshold_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.gmax, pl.nc1 * NGRP2, Q, scr.tau, top_k);
+        hipLaunchKernelGGL((affinity_tile_kernel<true, true, true>), dim3(qblocks, pl.nc2), dim3(256), lds2, s, mk, msq, qk, N, Q, pl.steps, 1,
+                           pl.spc2, (float *)nullptr, scr.tau, scr.cand_v, scr.cand_i, scr.cand_n, top_k, km);
+        hipLaunchKernelGGL(merge_readout_kernel<true>, dim3((Q + 3) / 4), dim3(256), 0, s, scr.cand_v, scr.cand_i, scr.cand_n, pl.nc2, Q,
+                           mv, mv_os, split ? 0 : k, readout, ro_os, gi, gw, rescore ? mk : nullptr, qk, top_k, km);
+    } else {
+        allow_big_lds(reinterpret_cast<const void *>(&affinity_tile_kernel<true, true>), lds2);
+        hipLaunchKernelGGL((affinity_tile_kernel<false>), dim3(qblocks, pl.nc1), dim3(256), lds1, s, mk, msq, qk, N, Q, pl.ns, pl.ss,
+                           pl.spc1, scr.gmax, (const float *)nullptr, (float *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, top_k, km);
+        hipLaunchKernelGGL(threshold_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.gmax, pl.nc1 * NGRP2, Q, scr.tau, top_k);
+        hipLaunchKernelGGL((affinity_tile_kernel<true, true>), dim3(qblocks, pl.nc2), dim3(256), lds2, s, mk, msq, qk, N, Q, pl.steps, 1,
+                           pl.spc2, (float *)nullptr, scr.tau, scr.cand_v, scr.cand_i, scr.cand_n, top_k, km);
+        hipLaunchKernelGGL(merge_readout_kernel<false>, dim3((Q + 3) / 4), dim3(256), 0, s, scr.cand_v, scr.cand_i, scr.cand_n, pl.nc2, Q,
+                           mv, mv_os, split ? 0 : k, readout, ro_os, gi, gw, rescore ? mk : nullptr, qk, top_k, km);
+    }
+    if (split) hipLaunchKernelGGL(gather_readout_kernel, dim3((Q + 3) / 4, k), dim3(256), 0, s, gi, gw, Q, mv, mv_os, readout, ro_os, top_k);
 }
 
 void merge_only_launch(const float *cand_v, const int32_t *cand_i, int NC, int Q, const float *mv, long mv_os, int k, int top_k,
                        float *readout, long ro_os, hipStream_t s) {
-    hipLaunchKernelGGL(merge_readout_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, cand_v, cand_i, (const int32_t *)nullptr, NC, Q,
-                       mv, mv_os, k, readout, ro_os, (int32_t *)nullptr, (float *)nullptr, (const float *)nullptr, (const float *)nullptr, top_k);
+    hipLaunchKernelGGL(merge_readout_kernel<false>, dim3((Q + 3) / 4), dim3(256), 0, s, cand_v, cand_i, (const int32_t *)nullptr, NC, Q,
+                       mv, mv_os, k, readout, ro_os, (int32_t *)nullptr, (float *)nullptr, (const float *)nullptr, (const float *)nullptr, top_k, KmArgs{});
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -181,6 +181,8 @@ def main():
     ap.add_argument("--qnet-weights", default="./model_weights/qnet/qnet.pth")
     ap.add_argument("--synthetic-weights", action="store_true", help="use the deterministic recipe (no checkpoints)")
     ap.add_argument("--top-k", type=int, default=50, help="rows of the memory bank each query reads, 1..50 (PropagationNetwork(top_k=...): 20 for STCN checkpoints, 50 for MiVOS)")
+    ap.add_argument("--km", type=float, default=None, metavar="SIGMA", help="kernelized memory read: standard deviation (1/16-scale positions) of the Gaussian "
+                    "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
     a = ap.parse_args()
     import torch.distributed as dist
 
@@ -188,7 +190,7 @@ def main():
     from .params import FusionNet, PropagationNetwork
     torch.set_grad_enabled(False)
     shard.init_from_env()                                  # one process per GPU; RCCL unless STCN_DIST_BACKEND says otherwise
-    prop, fuse, qnet = PropagationNetwork(top_k=a.top_k), FusionNet(), None
+    prop, fuse, qnet = PropagationNetwork(top_k=a.top_k, km=a.km), FusionNet(), None
     if a.policy == "qnet_mask":
         from .qnet import QualityNet
         qnet = QualityNet()

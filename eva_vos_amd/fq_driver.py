@@ -561,6 +561,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--lanes", type=int, default=2, help="videos in flight per GPU")
     ap.add_argument("--top-k", type=int, default=50, help="rows of the memory bank each query reads, 1..50 (PropagationNetwork(top_k=...): 20 for STCN checkpoints, 50 for MiVOS)")
+    ap.add_argument("--km", type=float, default=None, metavar="SIGMA", help="kernelized memory read: standard deviation (1/16-scale positions) of the Gaussian "
+                    "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
     a = ap.parse_args()
     import torch.distributed as dist
 
@@ -568,7 +570,7 @@ def main():
     from .params import FusionNet, PropagationNetwork
     torch.set_grad_enabled(False)
     shard.init_from_env()                                  # one process per GPU; RCCL unless STCN_DIST_BACKEND says otherwise
-    prop, fuse = PropagationNetwork(top_k=a.top_k), FusionNet()
+    prop, fuse = PropagationNetwork(top_k=a.top_k, km=a.km), FusionNet()
     if a.synthetic_weights:
         prop.load_state_dict(synth.recipe_state_dict(prop))
         fuse.load_state_dict(synth.recipe_state_dict(fuse))

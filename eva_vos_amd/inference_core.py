@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .params import check_top_k
+from .params import check_km, check_top_k
 
 _MODEL_CACHE: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 _PINNED_DOWNLOAD = os.environ.get("STCN_PINNED_DOWNLOAD", "1") != "0"      # 0: the reference's plain .cpu() (measurement aid)
@@ -84,7 +84,7 @@ def _pinned_result(shape, live: list):
 class _Model:
     """Owns one ``stcn_model`` handle (BN-folded, repacked weights on one device)."""
 
-    def __init__(self, prop_net, fuse_net, device_index: int, top_k: int = 50):
+    def __init__(self, prop_net, fuse_net, device_index: int, top_k: int = 50, km=None):
         lib = _lib.lib()
         keep = []
 
@@ -104,7 +104,7 @@ class _Model:
         p, n_p = descs(prop_net)
         f, n_f = descs(fuse_net) if fuse_net is not None else (None, 0)
         h = C.c_void_p()
-        opts = _lib.ModelOpts(top_k=int(top_k))
+        opts = _lib.ModelOpts(top_k=int(top_k), km=0.0 if km is None else float(km))
         _lib.check(lib.stcn_model_create_ex(device_index, p, n_p, f, n_f, C.byref(opts), C.byref(h)), "stcn_model_create_ex")
         self.handle = h
         self._finalizer = weakref.finalize(self, lib.stcn_model_destroy, h)
@@ -177,14 +177,27 @@ def _top_k_of(prop_net) -> int:
     return check_top_k(top_k)
 
 
-def _model_for(prop_net, fuse_net, device_index: int, top_k: int = 50) -> _Model:
+def _km_of(prop_net):
+    """The ``km`` a core built on ``prop_net`` reads with: ``prop_net.km`` (this package's weight container), else ``prop_net.memory.km``
+    (a live reference module: its EvalMemoryReader is a plain attribute, ``prop_model.memory.km = 5.6`` switches the kernelized read on),
+    else ``None`` - the plain read."""
+    if hasattr(prop_net, "km"):
+        km = prop_net.km
+    elif hasattr(getattr(prop_net, "memory", None), "km"):
+        km = prop_net.memory.km
+    else:
+        km = None
+    return check_km(km)
+
+
+def _model_for(prop_net, fuse_net, device_index: int, top_k: int = 50, km=None) -> _Model:
     """The engine works on a BN-folded, repacked SNAPSHOT of the weights.  The reference reads the live parameters, so the
     snapshot is keyed on a fingerprint of both modules' tensors: loading another checkpoint into the same module objects
     (one script evaluating several checkpoints) yields a fresh model.  A small LRU per (prop_net, device) keeps the last
     few snapshots, so alternating two fusion networks (or fuse_net / None) does not re-upload 218 MB per construction;
-    older ones die with their last engine.  ``top_k`` is part of the model (it changes results) and of the key: the same module
-    read with another ``top_k`` (the attribute was changed between two cores) is another model."""
-    key = (device_index, _fingerprint(prop_net), _fingerprint(fuse_net), int(top_k))      # outside the lock: it may sync the device
+    older ones die with their last engine.  ``top_k`` and ``km`` are part of the model (they change results) and of the key: the same
+    module read with another ``top_k`` or ``km`` (the attribute was changed between two cores) is another model."""
+    key = (device_index, _fingerprint(prop_net), _fingerprint(fuse_net), int(top_k), km)      # outside the lock: it may sync the device
     with _MODEL_LOCK:                       # engines may be created from several host threads (one per video)
         per_net = _MODEL_CACHE.setdefault(prop_net, {})
         hit = per_net.get(key)
@@ -197,7 +210,7 @@ def _model_for(prop_net, fuse_net, device_index: int, top_k: int = 50) -> _Model
         mine = [k for k in per_net if k[0] == device_index]
         for k in mine[:max(0, len(mine) - (_SNAPSHOTS_PER_DEVICE - 1))]:     # least recently used first
             del per_net[k]
-        model = _Model(prop_net, fuse_net, device_index, top_k)
+        model = _Model(prop_net, fuse_net, device_index, top_k, km)
         per_net[key] = (model, weakref.ref(fuse_net) if fuse_net is not None else None)
         return model
 
@@ -235,7 +248,7 @@ class InferenceCore:
         self.nh, self.nw = self.h + lh + uh, self.w + lw + uw
         self.kh, self.kw = self.nh // 16, self.nw // 16
         t_0 = time.perf_counter()
-        self._model = _model_for(prop_net, fuse_net, self.device.index or 0, _top_k_of(prop_net))
+        self._model = _model_for(prop_net, fuse_net, self.device.index or 0, _top_k_of(prop_net), _km_of(prop_net))
         t_1 = time.perf_counter()
         with torch.cuda.device(self.device):
             self._stream = torch.cuda.current_stream()
@@ -364,6 +377,13 @@ class InferenceCore:
         v = C.c_int32()
         _lib.check(_lib.lib().stcn_model_get_top_k(self._model.handle, C.byref(v)), "stcn_model_get_top_k")
         return int(v.value)
+
+    @property
+    def km(self):
+        """Standard deviation of the kernelized read's Gaussian as the engine's model holds it (fp32), or ``None``: the plain read."""
+        v = C.c_float()
+        _lib.check(_lib.lib().stcn_model_get_km(self._model.handle, C.byref(v)), "stcn_model_get_km")
+        return float(v.value) if v.value > 0 else None
 
     def stats(self) -> dict:
         s = _lib.Stats()

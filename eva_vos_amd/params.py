@@ -18,6 +18,7 @@ hand-written module classes.
 """
 from __future__ import annotations
 
+import math
 import numbers
 
 import torch.nn as nn
@@ -129,17 +130,30 @@ def check_top_k(top_k) -> int:
     return int(top_k)
 
 
+def check_km(km):
+    """``km`` as the HIP memory read takes it: ``None`` (the plain read) or a finite real > 0, the standard deviation of the Gaussian the
+    kernelized read weights the affinity with (reference EvalMemoryReader(top_k, km), prop_net.py:74-99)."""
+    if km is None:
+        return None
+    if isinstance(km, bool) or not isinstance(km, numbers.Real) or not math.isfinite(km) or not km > 0:
+        raise ValueError(f"km={km!r}: the kernelized memory read takes km=None or a finite km > 0 (reference prop_net.py:92-99)")
+    return float(km)
+
+
 class PropagationNetwork(_Bag):
     """Weights of the STCN propagation network (see module docstring).  ``top_k`` (1..50, default 50): the rows of the memory bank each
-    query reads; a hyper-parameter of the model, not a weight - it is no ``state_dict`` entry."""
+    query reads; ``km`` (``None`` or > 0, default ``None``): the kernelized read, as ``prop_model.memory.km`` of the reference.  Both are
+    hyper-parameters of the model, not weights - neither is a ``state_dict`` entry."""
 
-    def __init__(self, top_k=50):
+    def __init__(self, top_k=50, km=None):
         top_k = check_top_k(top_k)
+        km = check_km(km)
         super().__init__(value_encoder=_value_encoder(), key_encoder=_key_encoder(),
                          key_proj=_Bag(key_proj=_conv(1024, 64, 3)),
                          key_comp=_conv(1024, 512, 3),
                          decoder=_decoder())
         self.top_k = top_k
+        self.km = km
 
 
 class FusionNet(_Bag):

@@ -69,16 +69,24 @@ int stcn_model_destroy(stcn_model *m);
  *           (`top_k` of PropagationNetwork.__init__, model/propagation/prop_net.py:141, handed to MemoryReader and applied by
  *           softmax_w_top, prop_net.py:53-60).  Every capacity of the read is sized for 50; a larger value, and the reference's
  *           top_k=None (a dense softmax over the whole bank, another kernel family), return STCN_E_INVALID / are not expressible.
+ *   km      the kernelized memory read (`km` of EvalMemoryReader, prop_net.py:74-99; the reference's PropagationNetwork passes None and a
+ *           caller switches it on with `prop_model.memory.km = 5.6`): every memory row takes the position of the query it matches best in
+ *           the frame being read (prop_net.py:94-95), and exp(affinity - max) is multiplied by a Gaussian of standard deviation km (in
+ *           1/16-scale positions) around it BEFORE the top_k cut (make_gaussian :33-44, softmax_w_g_top :46-51).  A finite value > 0;
+ *           0 or negative = not given = the plain read, bit for bit; NaN / infinity return STCN_E_INVALID.  The fusion attention read
+ *           (AttentionMemory, prop_net.py:117-138) has no Gaussian in the reference and none here.
  * stcn_model_create(...) = stcn_model_create_ex(..., NULL, out).  Arguments are validated before the first device call.  Engines,
- * their clones and resets read the value from the model they share. */
+ * their clones and resets read the values from the model they share. */
 #define STCN_MAX_TOP_K  50
-typedef struct { int32_t top_k; } stcn_model_opts;
+typedef struct { int32_t top_k; float km; } stcn_model_opts;
 int stcn_model_create_ex(int device,
                          const stcn_weight_desc *prop, int n_prop,
                          const stcn_weight_desc *fuse, int n_fuse,
                          const stcn_model_opts *opts, stcn_model **out);
 /* The top_k the model runs with (PropagationNetwork.memory.top_k, prop_net.py:149). */
 int stcn_model_get_top_k(const stcn_model *m, int32_t *top_k);
+/* The km the model runs with (PropagationNetwork.memory.km); 0 = the plain read. */
+int stcn_model_get_km(const stcn_model *m, float *km);
 
 /* Create the per-video engine.
  *   images_dev : fp32 [1,T,3,H,W] (NCHW, normalized, unpadded), read once during this call.
@@ -201,6 +209,13 @@ int stcn_test_memory_read(void *stream, const float *mk, const float *mv, const 
  * topk_idx / topk_w are [Q,top_k].  stcn_test_memory_read(...) is the top_k = 50 case. */
 int stcn_test_memory_read_k(void *stream, const float *mk, const float *mv, const float *qk,
                             int N, int Q, int k, int top_k, int32_t *topk_idx, float *topk_w, float *readout);
+/* The kernelized read (EvalMemoryReader(top_k, km).get_affinity + readout, prop_net.py:80-115): the Q queries are Q / (h16 * w16) whole
+ * frames of h16 x w16 positions (a decode group; Q must be a multiple of h16 * w16), each frame read as the reference reads one frame.
+ * centres (may be NULL) [Q / (h16 * w16)][N] int32: per frame, the query of that frame every memory row matches best (argmax_idx,
+ * prop_net.py:94).  km > 0 finite; otherwise the limits of stcn_test_memory_read_k.  h16 = w16 = 0, km = 0, centres = NULL is that call. */
+int stcn_test_memory_read_km(void *stream, const float *mk, const float *mv, const float *qk,
+                             int N, int Q, int k, int top_k, int h16, int w16, float km, int32_t *centres,
+                             int32_t *topk_idx, float *topk_w, float *readout);
 
 /* Measurement hook of the same read: `iters` whole reads on caller-provided device data between two HIP events on
  * `stream` (scratch allocated outside the timed region); *ms = average per read; plan7 (may be NULL) receives the launch
@@ -210,6 +225,9 @@ int stcn_bench_memory_read(void *stream, const float *mk, const float *mv, const
 /* ... at another cut (prop_net.py:53-60 with top = top_k; same limits as stcn_test_memory_read_k); the call above is top_k = 50. */
 int stcn_bench_memory_read_k(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k,
                              int iters, float *readout, float *ms, int32_t *plan7);
+/* ... of the kernelized read (arguments as stcn_test_memory_read_km): the row-centre pass is inside the timed region. */
+int stcn_bench_memory_read_km(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k,
+                              int h16, int w16, float km, int iters, float *readout, float *ms, int32_t *plan7);
 
 /* Decoder + sigmoid + soft aggregation (prop_net.py:13-30,189-192; aggregate.py:22-37).
  * readout [k,hw16,512], f16_thin/f8/f4 NHWC -> logit4 [k,hw4] (may be NULL), agg [k+1,nh*nw]. */
