@@ -71,6 +71,7 @@ PROTOTYPES = {
     "stcn_bench_memory_read_k": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, C.POINTER(_F), C.POINTER(C.c_int32)]),
     "stcn_bench_memory_read_km": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, C.POINTER(_F), C.POINTER(C.c_int32)]),
     "stcn_memread_plan": (_I, [_I, _I, C.POINTER(C.c_int32)]),
+    "stcn_memread_scratch": (_I, [_I, C.POINTER(C.c_int64)]),
     "stcn_test_fail_at": (_I, [_I]),
     "stcn_test_side_delay_us": (_I, [_I]),
     "stcn_test_decode": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),

@@ -81,6 +81,42 @@ int plan_test_conv(int B, int H, int W, int Cin, int Cout, int K, int stride, in
     w.splitk = buf;
     return plan_conv(m, w, "t", ConvArgs(buf, Cin, B, H, W).strided(stride).out(buf).relu(flags & 1, (flags >> 1) & 1).splitk(splitk), p, pl);
 }
+// The read stcn_test_memory_read_km runs once and stcn_bench_memory_read_km times: the arguments checked (`who` names the hook in the
+// message), |mk|^2 and the scratch allocated - sized by memread_scratch_floats and nothing else -, the km scratch (|qk|^2 per query, the
+// packed row centres) when h16 / w16 / km / centres are not all zero, and the descriptor filled
+struct ReadRig {
+    DevBuf msq, cv, ci, cn, gm, tau, qsq, cen;
+    MemReadKm km{};
+    MemRead r{};
+    MemReadScratch scr{};
+    int init(const char *who, hipStream_t s, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k, int h16, int w16,
+             float sigma, int32_t *centres, int32_t *topk_idx, float *topk_w, float *readout) {
+        const bool bad = !mk || !mv || !qk || !readout || top_k < 1 || top_k > STCN_MAX_TOP_K || N < top_k || Q < 1 || k < 1;
+        if (bad) { set_error("%s: bad arguments (1 <= top_k <= %d, N >= top_k; top_k=%d N=%d)", who, STCN_MAX_TOP_K, top_k, N); return STCN_E_INVALID; }
+        const bool with_km = h16 != 0 || w16 != 0 || sigma != 0.f || centres;      // all zero: the plain read
+        // the kernelized read: km > 0 finite, the Q queries whole frames of h16 x w16 positions (16-bit coordinates)
+        const bool km_ok = std::isfinite(sigma) && sigma > 0.f && h16 >= 1 && w16 >= 1 && h16 < 32768 && w16 < 32768 && (long)h16 * w16 <= Q && Q % (h16 * w16) == 0;
+        if (with_km && !km_ok) { set_error("%s_km: bad arguments (km > 0 finite, Q a multiple of h16 * w16; km=%f h16=%d w16=%d Q=%d)", who, (double)sigma, h16, w16, Q); return STCN_E_INVALID; }
+        const MemReadScratchSizes sz = memread_scratch_floats(Q);
+        RC(msq.alloc((size_t)N + MEMREAD_MSQ_PAD)); RC(cv.alloc(sz.cand_v)); RC(ci.alloc(sz.cand_i)); RC(cn.alloc(sz.cand_n)); RC(gm.alloc(sz.gmax)); RC(tau.alloc(sz.tau));
+        scr = MemReadScratch{cv.p, reinterpret_cast<int32_t *>(ci.p), reinterpret_cast<int32_t *>(cn.p), gm.p, tau.p};
+        if (with_km) {
+            RC(qsq.alloc(Q)); RC(cen.alloc((size_t)(Q / (h16 * w16)) * memread_centre_stride(N)));
+            rowsumsq_launch(qk, Q, 64, qsq.p, s);
+            km = MemReadKm{sigma, h16, w16, qsq.p, (long)h16 * w16, reinterpret_cast<int32_t *>(cen.p), centres};
+        }
+        HIPCHK(hipMemsetAsync(msq.p, 0, ((size_t)N + MEMREAD_MSQ_PAD) * 4, s));
+        rowsumsq_launch(mk, N, 64, msq.p, s);
+        r.mk = mk; r.msq = msq.p; r.mv = mv; r.mv_os = (long)N * 512; r.N = N; r.qk = qk; r.Q = Q; r.k = k; r.top_k = top_k;
+        r.readout = readout; r.ro_os = (long)Q * 512; r.topk_idx = topk_idx; r.topk_w = topk_w; r.km = with_km ? &km : nullptr;
+        return STCN_OK;
+    }
+};
+void export_memread_plan(int N, int Q, int32_t *plan7) {
+    const MemReadPlan pl = memread_plan(N, Q);
+    const int32_t v[7] = {pl.steps, pl.ss, pl.ns, pl.nc1, pl.spc1, pl.nc2, pl.spc2};
+    for (int i = 0; i < 7; ++i) plan7[i] = v[i];
+}
 }  // namespace
 
 extern "C" {
@@ -242,44 +278,12 @@ int stcn_test_memory_read_k(void *stream, const float *mk, const float *mv, cons
     return stcn_test_memory_read_km(stream, mk, mv, qk, N, Q, k, top_k, 0, 0, 0.f, nullptr, topk_idx, topk_w, readout);
 }
 
-// the kernelized read's arguments of the two hooks below: km > 0 finite, the Q queries whole frames of h16 x w16 positions (16-bit coordinates)
-static bool km_args_ok(int Q, int h16, int w16, float km) {
-    return std::isfinite(km) && km > 0.f && h16 >= 1 && w16 >= 1 && h16 < 32768 && w16 < 32768 && (long)h16 * w16 <= Q && Q % (h16 * w16) == 0;
-}
-// scratch of the kernelized read for the hooks: |qk|^2 per query and the packed row centres
-struct KmScratch {
-    DevBuf qsq, cen;
-    MemReadKm km{};
-    int init(const float *qk, int N, int Q, int h16, int w16, float sigma, int32_t *centres, hipStream_t s) {
-        RC(qsq.alloc(Q)); RC(cen.alloc((size_t)(Q / (h16 * w16)) * memread_centre_stride(N)));
-        rowsumsq_launch(qk, Q, 64, qsq.p, s);
-        km = MemReadKm{sigma, h16, w16, qsq.p, (long)h16 * w16, reinterpret_cast<int32_t *>(cen.p), centres};
-        return STCN_OK;
-    }
-};
-
 int stcn_test_memory_read_km(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k, int h16, int w16,
                              float km, int32_t *centres, int32_t *topk_idx, float *topk_w, float *readout) {
-    const bool with_km = h16 != 0 || w16 != 0 || km != 0.f || centres;       // all zero: the plain read (stcn_test_memory_read_k)
-    if (!mk || !mv || !qk || !readout || top_k < 1 || top_k > STCN_MAX_TOP_K || N < top_k || Q < 1 || k < 1) {
-        set_error("stcn_test_memory_read: bad arguments (1 <= top_k <= %d, N >= top_k; top_k=%d N=%d)", STCN_MAX_TOP_K, top_k, N);
-        return STCN_E_INVALID;
-    }
-    if (with_km && !km_args_ok(Q, h16, w16, km)) {
-        set_error("stcn_test_memory_read_km: bad arguments (km > 0 finite, Q a multiple of h16 * w16; km=%f h16=%d w16=%d Q=%d)", (double)km, h16, w16, Q);
-        return STCN_E_INVALID;
-    }
     hipStream_t s = (hipStream_t)stream;
-    DevBuf msq, cv, ci, cn, gm, tau;
-    KmScratch ks;
-    const size_t pairs = memread_list_pairs(Q);
-    RC(msq.alloc(N + 64)); RC(cv.alloc(pairs * MEMREAD_MAX_TOPK)); RC(ci.alloc(pairs * MEMREAD_MAX_TOPK)); RC(cn.alloc(pairs));
-    RC(gm.alloc(pairs * 64)); RC(tau.alloc(Q));
-    if (with_km) RC(ks.init(qk, N, Q, h16, w16, km, centres, s));
-    HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(N + 64) * 4, s));
-    rowsumsq_launch(mk, N, 64, msq.p, s);
-    memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, topk_idx, topk_w,
-                       MemReadScratch{cv.p, reinterpret_cast<int32_t *>(ci.p), reinterpret_cast<int32_t *>(cn.p), gm.p, tau.p}, s, with_km ? &ks.km : nullptr);
+    ReadRig rig;
+    RC(rig.init("stcn_test_memory_read", s, mk, mv, qk, N, Q, k, top_k, h16, w16, km, centres, topk_idx, topk_w, readout));
+    memory_read_launch(rig.r, rig.scr, s);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     return STCN_OK;
@@ -299,43 +303,21 @@ int stcn_bench_memory_read_k(void *stream, const float *mk, const float *mv, con
 
 int stcn_bench_memory_read_km(void *stream, const float *mk, const float *mv, const float *qk, int N, int Q, int k, int top_k, int h16, int w16,
                               float km, int iters, float *readout, float *ms, int32_t *plan7) {
-    const bool with_km = h16 != 0 || w16 != 0 || km != 0.f;                    // all zero: the plain read (stcn_bench_memory_read_k)
-    if (!mk || !mv || !qk || !readout || !ms || top_k < 1 || top_k > STCN_MAX_TOP_K || N < top_k || Q < 1 || k < 1 || iters < 1) {
-        set_error("stcn_bench_memory_read: bad arguments (1 <= top_k <= %d, N >= top_k; top_k=%d N=%d)", STCN_MAX_TOP_K, top_k, N);
-        return STCN_E_INVALID;
-    }
-    if (with_km && !km_args_ok(Q, h16, w16, km)) {
-        set_error("stcn_bench_memory_read_km: bad arguments (km > 0 finite, Q a multiple of h16 * w16; km=%f h16=%d w16=%d Q=%d)", (double)km, h16, w16, Q);
-        return STCN_E_INVALID;
-    }
     hipStream_t s = (hipStream_t)stream;
-    DevBuf msq, cv, ci, cn, gm, tau;
-    KmScratch ks;
-    const size_t pairs = memread_list_pairs(Q);
-    RC(msq.alloc(N + 64)); RC(cv.alloc(pairs * MEMREAD_MAX_TOPK)); RC(ci.alloc(pairs * MEMREAD_MAX_TOPK)); RC(cn.alloc(pairs));
-    RC(gm.alloc(pairs * 64)); RC(tau.alloc(Q));
-    if (with_km) RC(ks.init(qk, N, Q, h16, w16, km, nullptr, s));
-    const MemReadKm *kmo = with_km ? &ks.km : nullptr;
-    HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(N + 64) * 4, s));
-    rowsumsq_launch(mk, N, 64, msq.p, s);
-    const MemReadScratch scr{cv.p, reinterpret_cast<int32_t *>(ci.p), reinterpret_cast<int32_t *>(cn.p), gm.p, tau.p};
+    if (!ms || iters < 1) { set_error("stcn_bench_memory_read: bad arguments (ms and iters >= 1 required; top_k=%d N=%d)", top_k, N); return STCN_E_INVALID; }
+    ReadRig rig;
+    RC(rig.init("stcn_bench_memory_read", s, mk, mv, qk, N, Q, k, top_k, h16, w16, km, nullptr, nullptr, nullptr, readout));
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    for (int it = 0; it < 2; ++it)
-        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, nullptr, nullptr, scr, s, kmo);
+    for (int it = 0; it < 2; ++it) memory_read_launch(rig.r, rig.scr, s);
     HIPCHK(hipEventRecord(e0, s));
-    for (int it = 0; it < iters; ++it)
-        memory_read_launch(mk, msq.p, qk, N, Q, mv, (long)N * 512, k, top_k, readout, (long)Q * 512, nullptr, nullptr, scr, s, kmo);
+    for (int it = 0; it < iters; ++it) memory_read_launch(rig.r, rig.scr, s);
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipEventSynchronize(e1));
     HIPCHK(hipEventElapsedTime(ms, e0, e1));
     *ms /= (float)iters;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (plan7) {
-        const MemReadPlan pl = memread_plan(N, Q);
-        const int v[7] = {pl.steps, pl.ss, pl.ns, pl.nc1, pl.spc1, pl.nc2, pl.spc2};
-        for (int i = 0; i < 7; ++i) plan7[i] = v[i];
-    }
+    if (plan7) export_memread_plan(N, Q, plan7);
     HIPCHK(hipGetLastError());
     return STCN_OK;
 }
@@ -354,9 +336,14 @@ int stcn_test_sweep_plan(int idx, int closest, int mem_freq, int cap, int32_t *o
 
 int stcn_memread_plan(int N, int Q, int32_t *plan7) {
     if (!plan7 || N < 1 || Q < 1) { set_error("stcn_memread_plan: bad arguments"); return STCN_E_INVALID; }
-    const MemReadPlan pl = memread_plan(N, Q);
-    const int v[7] = {pl.steps, pl.ss, pl.ns, pl.nc1, pl.spc1, pl.nc2, pl.spc2};
-    for (int i = 0; i < 7; ++i) plan7[i] = v[i];
+    export_memread_plan(N, Q, plan7);
+    return STCN_OK;
+}
+
+int stcn_memread_scratch(int Q, int64_t *sizes5) {
+    if (!sizes5 || Q < 1) { set_error("stcn_memread_scratch: bad arguments"); return STCN_E_INVALID; }
+    const MemReadScratchSizes sz = memread_scratch_floats(Q);
+    for (size_t i = 0, v[5] = {sz.cand_v, sz.cand_i, sz.cand_n, sz.gmax, sz.tau}; i < 5; ++i) sizes5[i] = (int64_t)v[i];
     return STCN_OK;
 }
 
@@ -384,13 +371,12 @@ int stcn_test_attention(void *stream, const float *mk, const float *qk, const fl
     if (!mk || !qk || !pos || !neg || !attn || kk < 1 || kk > STCN_MAX_OBJECTS + 1) { set_error("stcn_test_attention: bad arguments"); return STCN_E_INVALID; }
     hipStream_t s = (hipStream_t)stream;
     const int h = nh / 16, w = nw / 16;
-    DevBuf msq, pooled, amap, gm, cm, part;
-    RC(gm.alloc((size_t)256 * h * w)); RC(cm.alloc(h * w)); RC(part.alloc(attention_part_floats(kk, h * w)));
-    RC(msq.alloc(h * w + 64)); RC(pooled.alloc((size_t)std::max(20, attention_nchp(2 * kk)) * h * w)); RC(amap.alloc((size_t)kk * 2 * h * w));
+    DevBuf msq, pooled, amap, gm, part;
+    RC(gm.alloc((size_t)256 * h * w)); RC(part.alloc(attention_part_floats(kk, h * w)));
+    RC(msq.alloc(h * w + MEMREAD_MSQ_PAD)); RC(pooled.alloc((size_t)std::max(20, attention_nchp(2 * kk)) * h * w)); RC(amap.alloc((size_t)kk * 2 * h * w));
+    HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(h * w + MEMREAD_MSQ_PAD) * 4, s));
     rowsumsq_launch(mk, h * w, 64, msq.p, s);
-    HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(h * w + 64) * 4, s));
-    rowsumsq_launch(mk, h * w, 64, msq.p, s);
-    attention_read_launch(mk, msq.p, qk, pos, neg, kk, h, w, pooled.p, amap.p, attn, AttnScratch{gm.p, cm.p, part.p}, s);
+    attention_read_launch(mk, msq.p, qk, pos, neg, kk, h, w, pooled.p, amap.p, attn, AttnScratch{gm.p, part.p}, s);
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     return STCN_OK;

@@ -221,14 +221,18 @@ constexpr int MEMREAD_MAX_TOPK = 50;
 // spc1 sampled steps, pass 2 all steps in nc2 chunks of spc2
 struct MemReadPlan { int steps, ss, ns, nc1, spc1, nc2, spc2; };
 MemReadPlan memread_plan(int N, int Q);
-// upper bound of (chunks x queries) of either pass for Q queries: sizes the scratch below
-size_t memread_list_pairs(int Q);
-// P = memread_list_pairs(Q): cand_v / cand_i [P][50], cand_n [P], gmax [64 P], tau [Q]
+struct MemReadCost { double flop, bytes; };      // algorithmic FLOP and bytes of one read, as the profiler accounts them (km: the kernelized read)
+MemReadCost memread_cost(int N, int Q, int k, int top_k, bool km);
+// Scratch of a read of Q queries.  memread_scratch_floats(Q) is the one statement of its layout (memread.hip): the element counts of the five
+// buffers, for every bank size, top_k and object count.  Whoever allocates a MemReadScratch sizes it from these and from nothing else.
 struct MemReadScratch { float *cand_v; int32_t *cand_i; int32_t *cand_n; float *gmax; float *tau; };
+struct MemReadScratchSizes { size_t cand_v, cand_i, cand_n, gmax, tau; };
+MemReadScratchSizes memread_scratch_floats(int Q);
+constexpr int MEMREAD_MSQ_PAD = 64;     // readable floats behind the N values of msq: the read kernels fetch |mk|^2 in whole 64-row steps
 // dynamic LDS above 64 KB has to be opted into once per (device, kernel function)
 void allow_big_lds(const void *kernel, size_t lds);
 #if defined(__HIPCC__)
-// The one way the conv families launch a kernel.  ev: {start, stop} event pair that the dispatch itself fills (profiling on), or null -
+// The one way the conv families and the memory read launch a kernel.  ev: {start, stop} event pair that the dispatch itself fills (profiling on), or null -
 // then a plain launch: the engine is launch-bound and an unprofiled launch must ask the runtime for nothing more than that.
 template <typename... KArgs, typename... Args>
 static inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, hipEvent_t *ev, const Args &...args) {
@@ -243,14 +247,17 @@ static inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_
 // best query of every row within each frame
 struct MemReadKm { float sigma; int h16, w16; const float *qsq; long qsq_fs; int32_t *centre; int32_t *centre_idx; };
 long memread_centre_stride(int N);
-// mk [N,64], msq [N] (+ >= 64 readable floats of padding), qk [Q,64]; mv [k][N][512] with object stride mv_os; readout [k][Q][512] with
-// object stride ro_os.  top_k: 1 .. MEMREAD_MAX_TOPK rows per query, N >= top_k.  topk_idx/topk_w optional outputs [Q,top_k].
-// km == nullptr: the plain read, the kernels it always ran.
-void memory_read_launch(const float *mk, const float *msq, const float *qk, int N, int Q,
-                        const float *mv, long mv_os, int k, int top_k, float *readout, long ro_os,
-                        int32_t *topk_idx, float *topk_w, MemReadScratch scr, hipStream_t s, const MemReadKm *km = nullptr);
+// One read, described once; its callers (the engine's read_decode, the test hook, the bench hook) fill the fields by name.
+struct MemRead {
+    const float *mk, *msq, *mv; long mv_os; int N;      // bank: mk [N,64], msq [N] (+ MEMREAD_MSQ_PAD readable floats), mv [k][N][512] with object stride mv_os
+    const float *qk; int Q;                             // queries: qk [Q,64]
+    int k, top_k;                                       // objects; rows per query, 1 .. MEMREAD_MAX_TOPK, N >= top_k
+    float *readout; long ro_os; int32_t *topk_idx; float *topk_w;       // readout [k][Q][512] with object stride ro_os; topk_idx / topk_w optional [Q,top_k]
+    const MemReadKm *km;                                // null: the plain read, the kernels it always ran
+};
+void memory_read_launch(const MemRead &r, const MemReadScratch &scr, hipStream_t s);
 // fusion attention read: mk,qk [hw,64]; pos,neg [kk][16h*16w planes] -> attn [kk][2][nh*nw]; pooled: scratch of attention_nchp(2 kk) * h * w floats
-struct AttnScratch { float *gmax, *cmax, *part; };   // [256][hw], [hw], attention_part_floats(kk, hw) ([16][hw][19] up to 8 objects)
+struct AttnScratch { float *gmax, *part; };   // [256][hw], attention_part_floats(kk, hw) ([16][hw][19] up to 8 objects)
 int attention_nchp(int nch);                          // channels 2 kk padded to the widths the pass kernel is instantiated for
 size_t attention_part_floats(int kk, int hw);
 // pos == nullptr: `pooled` already holds attention_pool_launch's output for this interaction
@@ -273,10 +280,6 @@ void jf_counts_launch(const uint8_t *gt, const uint8_t *pred, int T, int H, int 
 void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *noobj,
                         int Tn, int H, int W, int radius, double no_object, uint8_t *gen, uint8_t *bmap, int *counts, int T_all, double *quality,
                         int *select, hipStream_t s, int t0);
-
-// debug/stress: launch ONLY the merge stage on prepared candidate lists (cand_v/cand_i [NC][Q][50], top_k entries used of each)
-void merge_only_launch(const float *cand_v, const int32_t *cand_i, int NC, int Q, const float *mv, long mv_os, int k, int top_k,
-                       float *readout, long ro_os, hipStream_t s);
 
 // pure fp32-MFMA load (no memory traffic): launches `grid` workgroups of 12 waves x iters x 12 MFMAs, returns the FLOP of the launch
 double mfma_probe_launch(float *out, int grid, int iters, hipStream_t s);

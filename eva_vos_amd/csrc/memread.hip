@@ -31,6 +31,9 @@
 //   row_centre_kernel finds the centres (one more affinity walk, roles of keys and queries swapped, per frame of a decode group);
 //   the KM instantiations of affinity_tile_kernel / merge_readout_kernel add the bias in the tile epilogue / to the fp64 re-score.
 //   Without km the launch path runs the instantiations it always ran.
+#include <hip/hip_ext.h>
+
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -753,20 +756,21 @@ __global__ __launch_bounds__(256) void gather_readout_kernel(const int32_t *__re
     *reinterpret_cast<f32x4 *>(dst + 256) = a1;
 }
 
-// pass 2 runs with ONE key tile buffer: 50 KB of LDS per workgroup = 3 workgroups (12 waves) per CU instead of 2; the third
-// workgroup hides the second barrier per step and the LDS-atomic latencies of the appends (+3..5 % on large banks, round 2)
-static constexpr bool memread_single_buffer() { return true; }
+// Pass 2 runs with ONE key tile buffer (SINGLE): 50 KB of LDS per workgroup = 3 workgroups (12 waves) per CU instead of 2; the third
+// workgroup hides the second barrier per step and the LDS-atomic latencies of the appends (+3..5 % on large banks, round 2).
+// Workgroups one round of co-resident workgroups holds: pass 1 (33 KB of LDS) 4 per CU, pass 2 3 per CU, of 256 CUs
+static constexpr int RESIDENT1 = 1024, RESIDENT2 = 768;
 
 MemReadPlan memread_plan(int N, int Q) {
     MemReadPlan p;
     p.steps = (N + HROWS - 1) / HROWS;
     const int qblocks = (Q + 63) / 64;
     // pass 1 samples every ss-th step: at least ~48 sampled steps so that the 64 * nc1 row groups are all populated
-    static const int ss_env = [] { const char *e = getenv("STCN_MEMREAD_SAMPLE"); return e ? atoi(e) : 0; }();
+    static const int ss_env = env_int("STCN_MEMREAD_SAMPLE", 0);
     p.ss = ss_env > 0 ? ss_env : (p.steps >= 768 ? 8 : (p.steps >= 192 ? 4 : (p.steps >= 96 ? 2 : 1)));
     p.ns = (p.steps + p.ss - 1) / p.ss;
     // chunks: as many as keep qblocks * nc within ONE round of co-resident workgroups (a few workgroups beyond the round
-    // would run alone afterwards and double the time): pass 2 holds 2 workgroups per CU (LDS lists), pass 1 up to 4
+    // would run alone afterwards and double the time)
     auto chunks = [&](int steps, int resident, int hi, int *spc) {
         int nc = resident / qblocks;
         nc = nc < 1 ? 1 : (nc > hi ? hi : nc);
@@ -774,60 +778,63 @@ MemReadPlan memread_plan(int N, int Q) {
         *spc = (steps + nc - 1) / nc;
         return (steps + *spc - 1) / *spc;
     };
-    p.nc1 = chunks(p.ns, 1024, MAXCHUNK1, &p.spc1);         // 64 maxima per chunk and query: <= 512 for threshold_kernel
-    p.nc2 = chunks(p.steps, memread_single_buffer() ? 768 : 512, MAXCHUNK2, &p.spc2);
+    p.nc1 = chunks(p.ns, RESIDENT1, MAXCHUNK1, &p.spc1);    // 64 maxima per chunk and query: <= 512 for threshold_kernel
+    p.nc2 = chunks(p.steps, RESIDENT2, MAXCHUNK2, &p.spc2);
     return p;
 }
-// bound of nc * Q over both passes: nc1 <= min(8, 1024 / qblocks) and nc2 <= max(1, 512 / qblocks) with Q <= 64 qblocks
-size_t memread_list_pairs(int Q) { return (size_t)65536 + (size_t)Q + 64; }
+
+// algorithmic work of one read.  FLOP: the N x Q x 64 affinity - walked once more by the kernelized read, for the row centres -
+// and the top_k-sparse read-out.  Bytes: the key bank (+ |mk|^2) and the queries once, top_k value rows of 2 KB per query and object, the read-out once
+MemReadCost memread_cost(int N, int Q, int k, int top_k, bool km) {
+    const double n = N, q = Q;
+    return {(km ? 4.0 : 2.0) * n * q * 64 + 2.0 * k * q * top_k * 512, 4.0 * (n * 65 + q * 64 + k * q * top_k * 512 + k * q * 512)};
+}
+
+// Bound of (chunks x queries) of either pass.  Q <= 64 qblocks, so nc1 <= max(1, min(MAXCHUNK1, RESIDENT1 / qblocks)) gives
+// nc1 * Q <= max(Q, 64 * RESIDENT1) = max(Q, 65536), and nc2 <= max(1, min(MAXCHUNK2, RESIDENT2 / qblocks)) gives nc2 * Q <= max(Q, 49152)
+static size_t memread_list_pairs(int Q) { return (size_t)64 * RESIDENT1 + (size_t)Q + 64; }
+// THE scratch layout of a read of Q queries, P = memread_list_pairs(Q): cand_v / cand_i [nc2][Q][50] the chunk lists of pass 2 (<= P * 50),
+// cand_n [nc2][Q] their lengths (<= P), tau [Q] the thresholds, gmax [Q][nc1 * 64] the group maxima of pass 1 (<= P * 64) that threshold_kernel
+// reads - and, free from then on, the selection of the split read (k > 1, no topk outputs): indices [Q][50] at gmax, weights [Q][50] at
+// gmax + Q * 50, written by merge_readout_kernel and read by gather_readout_kernel
+MemReadScratchSizes memread_scratch_floats(int Q) {
+    const size_t pairs = memread_list_pairs(Q);
+    return {pairs * TOPK, pairs * TOPK, pairs, std::max(pairs * NGRP2, (size_t)2 * Q * TOPK), (size_t)Q};
+}
 
 long memread_centre_stride(int N) { return (long)((N + HROWS - 1) / HROWS) * HROWS; }
 
-void memory_read_launch(const float *mk, const float *msq, const float *qk, int N, int Q, const float *mv,
-                        long mv_os, int k, int top_k, float *readout, long ro_os, int32_t *topk_idx, float *topk_w,
-                        MemReadScratch scr, hipStream_t s, const MemReadKm *kmo) {
-    const MemReadPlan pl = memread_plan(N, Q);
-    const int qblocks = (Q + 63) / 64;
-    static const bool rescore = [] { const char *e = getenv("STCN_MEMREAD_RESCORE"); return !e || atoi(e) != 0; }();      // measurement aid: 0 = plain fp32 cut
-    const size_t lds1 = (size_t)2 * KT_FLOATS * sizeof(float);
-    const bool single = memread_single_buffer();
-    const size_t lds2 = (single ? lds1 / 2 : lds1) + (size_t)4 * LISTS_PER_WAVE * sizeof(float);
-    // several objects: merge once per query (indices / weights [Q][top_k] into the group-maxima scratch, free since threshold_kernel),
-    // then gather with one wave per (query, object)
-    const bool split = !(k == 1 || topk_idx || topk_w);
-    int32_t *gi = split ? reinterpret_cast<int32_t *>(scr.gmax) : topk_idx;
-    float *gw = split ? scr.gmax + (size_t)Q * TOPK : topk_w;
-    const KmArgs km = kmo ? KmArgs{kmo->centre, memread_centre_stride(N), kmo->h16 * kmo->w16, kmo->w16, 1.f / (2.f * kmo->sigma * kmo->sigma)} : KmArgs{};
-    if (kmo) {   // the kernelized read: centres of every bank row per query frame, then the same sequence on the biased score
+// the launches of one read; KM: the kernelized read - centres of every bank row per query frame first, then the same sequence on the biased score
+template <bool KM>
+static void memory_read_sequence(const MemRead &r, const MemReadScratch &scr, hipStream_t s) {
+    const MemReadPlan pl = memread_plan(r.N, r.Q);
+    const int N = r.N, Q = r.Q, top_k = r.top_k, qblocks = (Q + 63) / 64;
+    static const bool rescore = env_on("STCN_MEMREAD_RESCORE");      // measurement aid: 0 = plain fp32 cut
+    const size_t lds1 = (size_t)2 * KT_FLOATS * sizeof(float);                                    // pass 1: two key tile buffers
+    const size_t lds2 = lds1 / 2 + (size_t)4 * LISTS_PER_WAVE * sizeof(float);                    // pass 2: one, and the lists of the 4 waves
+    // several objects: merge once per query (indices / weights [Q][top_k] into the gmax alias of memread_scratch_floats), then gather
+    // with one wave per (query, object)
+    const bool split = !(r.k == 1 || r.topk_idx || r.topk_w);
+    int32_t *gi = split ? reinterpret_cast<int32_t *>(scr.gmax) : r.topk_idx;
+    float *gw = split ? scr.gmax + (size_t)Q * TOPK : r.topk_w;
+    KmArgs km{};
+    if constexpr (KM) {
         constexpr int CW = 4, CB = 2;
-        hipLaunchKernelGGL((row_centre_kernel<CW, CB>), dim3((N + 16 * CB * CW - 1) / (16 * CB * CW), Q / km.hw16), dim3(64 * CW), 0, s, mk, N, qk, kmo->qsq,
-                           kmo->qsq_fs, km.hw16, km.w16, kmo->centre, km.cstride, kmo->centre_idx);
-        allow_big_lds(reinterpret_cast<const void *>(&affinity_tile_kernel<true, true, true>), lds2);
-        hipLaunchKernelGGL((affinity_tile_kernel<false, false, true>), dim3(qblocks, pl.nc1), dim3(256), lds1, s, mk, msq, qk, N, Q, pl.ns, pl.ss,
-                           pl.spc1, scr.gmax, (const float *)nullptr, (float *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, top_k, km);
-        hipLaunchKernelGGL(threshold_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.gmax, pl.nc1 * NGRP2, Q, scr.tau, top_k);
-        hipLaunchKernelGGL((affinity_tile_kernel<true, true, true>), dim3(qblocks, pl.nc2), dim3(256), lds2, s, mk, msq, qk, N, Q, pl.steps, 1,
-                           pl.spc2, (float *)nullptr, scr.tau, scr.cand_v, scr.cand_i, scr.cand_n, top_k, km);
-        hipLaunchKernelGGL(merge_readout_kernel<true>, dim3((Q + 3) / 4), dim3(256), 0, s, scr.cand_v, scr.cand_i, scr.cand_n, pl.nc2, Q,
-                           mv, mv_os, split ? 0 : k, readout, ro_os, gi, gw, rescore ? mk : nullptr, qk, top_k, km);
-    } else {
-        allow_big_lds(reinterpret_cast<const void *>(&affinity_tile_kernel<true, true>), lds2);
-        hipLaunchKernelGGL((affinity_tile_kernel<false>), dim3(qblocks, pl.nc1), dim3(256), lds1, s, mk, msq, qk, N, Q, pl.ns, pl.ss,
-                           pl.spc1, scr.gmax, (const float *)nullptr, (float *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, top_k, km);
-        hipLaunchKernelGGL(threshold_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, scr.gmax, pl.nc1 * NGRP2, Q, scr.tau, top_k);
-        hipLaunchKernelGGL((affinity_tile_kernel<true, true>), dim3(qblocks, pl.nc2), dim3(256), lds2, s, mk, msq, qk, N, Q, pl.steps, 1,
-                           pl.spc2, (float *)nullptr, scr.tau, scr.cand_v, scr.cand_i, scr.cand_n, top_k, km);
-        hipLaunchKernelGGL(merge_readout_kernel<false>, dim3((Q + 3) / 4), dim3(256), 0, s, scr.cand_v, scr.cand_i, scr.cand_n, pl.nc2, Q,
-                           mv, mv_os, split ? 0 : k, readout, ro_os, gi, gw, rescore ? mk : nullptr, qk, top_k, km);
+        km = KmArgs{r.km->centre, memread_centre_stride(N), r.km->h16 * r.km->w16, r.km->w16, 1.f / (2.f * r.km->sigma * r.km->sigma)};
+        launch(row_centre_kernel<CW, CB>, dim3((N + 16 * CB * CW - 1) / (16 * CB * CW), Q / km.hw16), dim3(64 * CW), 0, s, nullptr, r.mk, N, r.qk, r.km->qsq,
+               r.km->qsq_fs, km.hw16, km.w16, r.km->centre, km.cstride, r.km->centre_idx);
     }
-    if (split) hipLaunchKernelGGL(gather_readout_kernel, dim3((Q + 3) / 4, k), dim3(256), 0, s, gi, gw, Q, mv, mv_os, readout, ro_os, top_k);
+    launch(affinity_tile_kernel<false, false, KM>, dim3(qblocks, pl.nc1), dim3(256), lds1, s, nullptr, r.mk, r.msq, r.qk, N, Q, pl.ns, pl.ss, pl.spc1,
+           scr.gmax, (const float *)nullptr, (float *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, top_k, km);
+    launch(threshold_kernel, dim3((Q + 3) / 4), dim3(256), 0, s, nullptr, scr.gmax, pl.nc1 * NGRP2, Q, scr.tau, top_k);
+    launch(affinity_tile_kernel<true, true, KM>, dim3(qblocks, pl.nc2), dim3(256), lds2, s, nullptr, r.mk, r.msq, r.qk, N, Q, pl.steps, 1, pl.spc2,
+           (float *)nullptr, scr.tau, scr.cand_v, scr.cand_i, scr.cand_n, top_k, km);
+    launch(merge_readout_kernel<KM>, dim3((Q + 3) / 4), dim3(256), 0, s, nullptr, scr.cand_v, scr.cand_i, scr.cand_n, pl.nc2, Q, r.mv, r.mv_os,
+           split ? 0 : r.k, r.readout, r.ro_os, gi, gw, rescore ? r.mk : nullptr, r.qk, top_k, km);
+    if (split) launch(gather_readout_kernel, dim3((Q + 3) / 4, r.k), dim3(256), 0, s, nullptr, gi, gw, Q, r.mv, r.mv_os, r.readout, r.ro_os, top_k);
 }
 
-void merge_only_launch(const float *cand_v, const int32_t *cand_i, int NC, int Q, const float *mv, long mv_os, int k, int top_k,
-                       float *readout, long ro_os, hipStream_t s) {
-    hipLaunchKernelGGL(merge_readout_kernel<false>, dim3((Q + 3) / 4), dim3(256), 0, s, cand_v, cand_i, (const int32_t *)nullptr, NC, Q,
-                       mv, mv_os, k, readout, ro_os, (int32_t *)nullptr, (float *)nullptr, (const float *)nullptr, (const float *)nullptr, top_k, KmArgs{});
-}
+void memory_read_launch(const MemRead &r, const MemReadScratch &scr, hipStream_t s) { r.km ? memory_read_sequence<true>(r, scr, s) : memory_read_sequence<false>(r, scr, s); }
 
 // ------------------------------------------------------------------------------------------------
 // Fusion attention read (prop_net.py:117-138,198-211): W = softmax over memory rows of the T=1
@@ -862,7 +869,7 @@ int attention_nchp(int nch) { return nch <= 4 ? 4 : (nch <= 8 ? 8 : (nch <= 12 ?
 // floats per (chunk, query) of the partial sums: the softmax denominator + one per channel (19 up to 8 objects, as sized since round 2)
 static int attention_part_stride(int nch) { return 1 + (nch <= 18 ? 18 : nch); }
 size_t attention_part_floats(int kk, int hw) { return (size_t)MAXCHUNK * hw * attention_part_stride(2 * kk); }
-// pass 2 of the attention read: per (query block, row chunk) partial sums of e = exp(S - cmax[q]), cmax = exact column maximum:
+// pass 2 of the attention read: per (query block, row chunk) partial sums of e = exp(S - cm[q]), cm = the exact column maximum:
 //   part[chunk][q][0] = sum_m e,  part[chunk][q][1 + c] = sum_m e * pooled[c][m]
 template <int WAVES, int NCHP>
 __global__ __launch_bounds__(64 * WAVES) void attention_pass_kernel(

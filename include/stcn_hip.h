@@ -250,6 +250,10 @@ int stcn_test_fusion(const stcn_model *m, void *stream, const float *img, const 
  * plan7 = { 64-row steps, pass-1 sample stride, sampled steps, pass-1 chunks, steps per pass-1 chunk, pass-2 chunks,
  * steps per pass-2 chunk }.  Lets tests assert WHICH plan (sample stride 1/2/4/8) a comparison exercised. */
 int stcn_memread_plan(int N, int Q, int32_t *plan7);
+/* Scratch of that read for Q queries, in elements (what the engine and the hooks allocate; it depends on Q alone):
+ * sizes5 = { cand_v, cand_i, cand_n, gmax, tau }.  Every (N, Q) plan fits: nc2 * Q * 50 <= cand_v = cand_i, nc2 * Q <= cand_n,
+ * nc1 * Q * 64 <= gmax, 2 * Q * 50 <= gmax (the selection of a read of several objects reuses it), Q <= tau.  Works without a GPU. */
+int stcn_memread_scratch(int Q, int64_t *sizes5);
 
 /* Engine buffers (workspaces, key cache, memory bank, packed clip) come from a per-device pool: a destroyed engine's buffers
  * wait there for the next engine of the same sizes (the reference's drivers build one InferenceCore per sample; a hipFree

@@ -436,6 +436,34 @@ def test_near_tie_queries_are_the_only_ones_that_differ():
     assert (gro - own).abs().max() / own.abs().max() < 2e-5
 
 
+#               N     Q   k  top_k  (h16, w16, km)
+SPLIT_READS = [(1620, 333, 2, 50, None), (1620, 333, 2, 20, None), (240, 80, 2, 50, (8, 10, 5.6))]
+
+
+@pytest.mark.parametrize("N,Q,k,top_k,km", SPLIT_READS, ids=["top50", "top20", "km-frame"])
+def test_read_of_several_objects_without_topk_outputs_is_the_read_with_them(N, Q, k, top_k, km):
+    """The read the engine runs and no other hook test reaches: k > 1 and neither topk_idx nor topk_w.  merge_readout_kernel then leaves the
+    selection in the scratch of pass 1's group maxima and gather_readout_kernel gathers with one wave per (query, object); with the
+    outputs given the merge kernel gathers itself.  Both add the same rows in the same order: the suite's 2e-5 (bit equality is not
+    promised).  Banks: a fixed case of test_memory_read_matches_oracle at both cuts, and the "frame" bank of test_gpu_km (same draw)."""
+    g = torch.Generator().manual_seed(N + Q)
+    mk, qk, mv = dev(torch.randn(N, 64, generator=g)), dev(torch.randn(Q, 64, generator=g)), dev(torch.randn(k, N, 512, generator=g))
+    h16, w16, sigma = km or (0, 0, 0.0)
+
+    def read(outputs):
+        idx = torch.empty(Q, top_k, dtype=torch.int32, device="cuda") if outputs else None
+        w = torch.empty(Q, top_k, device="cuda") if outputs else None
+        ro = torch.full((k, Q, 512), float("nan"), device="cuda")          # every read-out element must be written
+        call("stcn_test_memory_read_km", stream(), mk, mv, qk, N, Q, k, top_k, h16, w16, float(sigma), None, idx, w, ro)
+        return ro.cpu()
+
+    whole, split = read(True), read(False)
+    assert torch.isfinite(whole).all() and torch.isfinite(split).all()
+    err = (split - whole).abs().max().item() / whole.abs().max().item()
+    print(f"N={N} Q={Q} k={k} top_k={top_k} km={km}: split against merged read-out, max relative difference {err:.2e}")
+    assert err < 2e-5, err
+
+
 @pytest.mark.parametrize("kk", [2, 4, 6, 9, 10, 11, 17, 21, 33])
 def test_attention_read_matches_oracle(kk):
     """kk = mask rows (objects + background): 2 kk channels.  Up to 9 rows run in one pass of the instantiated widths (4 / 8 / 12 / 20
