@@ -37,7 +37,7 @@ class Stats(C.Structure):
 
 
 # name -> (restype, argtypes); kept in one table so tests can check every declared symbol is exported
-_P, _I, _F, _D = C.c_void_p, C.c_int, C.c_float, C.c_double
+_P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 PROTOTYPES = {
     "stcn_last_error": (C.c_char_p, []),
     "stcn_version": (C.c_char_p, []),
@@ -46,6 +46,16 @@ PROTOTYPES = {
     "stcn_model_get_top_k": (_I, [_P, C.POINTER(C.c_int32)]),
     "stcn_model_get_km": (_I, [_P, C.POINTER(C.c_float)]),
     "stcn_model_destroy": (_I, [_P]),
+    "stcn_fusion_model_create": (_I, [_I, C.POINTER(WeightDesc), _I, C.POINTER(_P)]),
+    "stcn_stage_create": (_I, [_P, _I, _I, _I, _P, C.POINTER(_P)]),
+    "stcn_stage_destroy": (_I, [_P]),
+    "stcn_stage_encode_key": (_I, [_P] * 7),
+    "stcn_stage_encode_value": (_I, [_P, _P, _P, _P, _I, _P]),
+    "stcn_stage_segment": (_I, [_P, _P, _L, _P, _L, _L, _I, _I, _P, _P, _P, _P, _P]),
+    "stcn_stage_attention": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "stcn_stage_fusion": (_I, [_P, _P, _P, _P, _P, _F, _F, _P]),
+    "stcn_aggregate_wbg": (_I, [_P, _P, _I, _L, _I, _I, _P]),
+    "stcn_test_transpose": (_I, [_P, _P, _P, _I, _I, _I, _L, _L, _I]),
     "stcn_engine_create": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(_P)]),
     "stcn_engine_create_ex": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(EngineOpts), C.POINTER(_P)]),
     "stcn_engine_get_opts": (_I, [_P, C.POINTER(EngineOpts)]),

@@ -147,14 +147,14 @@ void upsample2x_add_launch(const float *x, const float *skip, float *u, int B, i
 
 // aggregate_wbg (aggregate.py:22-37): odds / sum(odds) after clamping.  MAXOBJ = 8 (every caller of the reference: k = 1, BASELINE config 3:
 // k = 5) or STCN_MAX_OBJECTS: the probabilities of a pixel stay in registers either way, the arithmetic and its order are the same.
+// the odds of the k + 1 rows (background first) and their sum
 template <int MAXOBJ>
-__device__ __forceinline__ void aggregate_store(const float *p, int k, float *agg, long stride, long pix) {
+__device__ __forceinline__ float aggregate_odds(const float *p, int k, float *odds) {
     float bg = 1.f;
 #pragma unroll
     for (int o = 0; o < MAXOBJ; ++o)
         if (o < k) bg *= (1.f - p[o]);
     const float lo = 1e-7f, hi = 1.f - 1e-7f;
-    float odds[MAXOBJ + 1];
     float q = fminf(fmaxf(bg, lo), hi);
     odds[0] = q / (1.f - q);
     float tot = odds[0];
@@ -166,6 +166,12 @@ __device__ __forceinline__ void aggregate_store(const float *p, int k, float *ag
             tot += odds[o + 1];
         }
     }
+    return tot;
+}
+template <int MAXOBJ>
+__device__ __forceinline__ void aggregate_store(const float *p, int k, float *agg, long stride, long pix) {
+    float odds[MAXOBJ + 1];
+    const float tot = aggregate_odds<MAXOBJ>(p, k, odds);
     agg[pix] = odds[0] / tot;
 #pragma unroll
     for (int o = 0; o < MAXOBJ; ++o)
@@ -173,7 +179,8 @@ __device__ __forceinline__ void aggregate_store(const float *p, int k, float *ag
 }
 
 // Decoder tail (prop_net.py:27-29,192) + aggregate: logit4 -> bilinear x4 -> sigmoid -> aggregate
-template <int MAXOBJ>
+// AGG = false: the per-object probabilities themselves, out [k][H * W] with row stride `stride` - what segment_with_query returns (prop_net.py:192)
+template <int MAXOBJ, bool AGG = true>
 __global__ void up4_sigmoid_aggregate_kernel(const float *__restrict__ logit4, int k, int h4, int w4,
                                              float *__restrict__ agg, long stride, long obj_stride, long logit_gs, long agg_gs) {
     const int H = 4 * h4, W = 4 * w4;
@@ -197,7 +204,13 @@ __global__ void up4_sigmoid_aggregate_kernel(const float *__restrict__ logit4, i
             p[o] = sigmoidf_(v);
         }
     }
-    aggregate_store<MAXOBJ>(p, k, agg, stride, i);
+    if constexpr (AGG) {
+        aggregate_store<MAXOBJ>(p, k, agg, stride, i);
+    } else {
+#pragma unroll
+        for (int o = 0; o < MAXOBJ; ++o)
+            if (o < k) agg[o * stride + i] = p[o];
+    }
 }
 void up4_sigmoid_aggregate_launch(const float *logit4, int k, int h4, int w4, float *agg, long agg_stride,
                                   hipStream_t s, long obj_stride, int G, long logit_gs, long agg_gs) {
@@ -207,6 +220,49 @@ void up4_sigmoid_aggregate_launch(const float *logit4, int k, int h4, int w4, fl
         hipLaunchKernelGGL(up4_sigmoid_aggregate_kernel<8>, grid, dim3(256), 0, s, logit4, k, h4, w4, agg, agg_stride, os, logit_gs, agg_gs);
     else
         hipLaunchKernelGGL(up4_sigmoid_aggregate_kernel<STCN_MAX_OBJECTS>, grid, dim3(256), 0, s, logit4, k, h4, w4, agg, agg_stride, os, logit_gs, agg_gs);
+}
+void up4_sigmoid_launch(const float *logit4, int k, int h4, int w4, float *prob, hipStream_t s) {
+    const dim3 grid(nblocks(16L * h4 * w4), 1);
+    const long hw4 = (long)h4 * w4;
+    if (k <= 8)
+        hipLaunchKernelGGL((up4_sigmoid_aggregate_kernel<8, false>), grid, dim3(256), 0, s, logit4, k, h4, w4, prob, 16 * hw4, hw4, 0L, 0L);
+    else
+        hipLaunchKernelGGL((up4_sigmoid_aggregate_kernel<STCN_MAX_OBJECTS, false>), grid, dim3(256), 0, s, logit4, k, h4, w4, prob, 16 * hw4, hw4, 0L, 0L);
+}
+
+// aggregate_wbg on probabilities (aggregate.py:22-37): prob [k][npix] -> out [k + 1][npix] (keep_bg) or the k object rows [k][npix].
+// Soft: odds / sum(odds), the arithmetic of aggregate_store (softmax(log odds) without the log / exp round trip).  hard: the logits times
+// 1000 before the softmax - odds^1000 is not representable, so that case takes the logarithm and the usual max-shifted softmax.
+template <int MAXOBJ>
+__global__ void aggregate_wbg_kernel(const float *__restrict__ prob, int k, long npix, int keep_bg, int hard, float *__restrict__ out) {
+    const long i = blockIdx.x * 256L + threadIdx.x;
+    if (i >= npix) return;
+    float p[MAXOBJ];
+#pragma unroll
+    for (int o = 0; o < MAXOBJ; ++o) p[o] = o < k ? prob[o * npix + i] : 0.f;
+    float odds[MAXOBJ + 1];
+    float tot = aggregate_odds<MAXOBJ>(p, k, odds);
+    if (hard) {
+        float mx = -INFINITY;
+#pragma unroll
+        for (int o = 0; o <= MAXOBJ; ++o)
+            if (o <= k) { odds[o] = 1000.f * logf(odds[o]); mx = fmaxf(mx, odds[o]); }
+        tot = 0.f;
+#pragma unroll
+        for (int o = 0; o <= MAXOBJ; ++o)
+            if (o <= k) { odds[o] = expf(odds[o] - mx); tot += odds[o]; }
+    }
+    const int up = keep_bg ? 0 : 1;                      // without the background row the object rows move up by one
+    if (keep_bg) out[i] = odds[0] / tot;
+#pragma unroll
+    for (int o = 1; o <= MAXOBJ; ++o)
+        if (o <= k) out[(o - up) * npix + i] = odds[o] / tot;
+}
+void aggregate_wbg_launch(const float *prob, int k, long npix, int keep_bg, int hard, float *out, hipStream_t s) {
+    if (k <= 8)
+        hipLaunchKernelGGL(aggregate_wbg_kernel<8>, dim3(nblocks(npix)), dim3(256), 0, s, prob, k, npix, keep_bg, hard, out);
+    else
+        hipLaunchKernelGGL(aggregate_wbg_kernel<STCN_MAX_OBJECTS>, dim3(nblocks(npix)), dim3(256), 0, s, prob, k, npix, keep_bg, hard, out);
 }
 
 // fusion tail (inference_core.py:203-207): sigmoid(fuse_net(...)) per object -> aggregate

@@ -51,6 +51,7 @@ struct Model {
     int device = 0;
     std::map<std::string, ConvW> conv;
     CbamW cbam{};
+    bool has_prop = false;                 // the propagation network's layers are there (false: stcn_fusion_model_create, FusionNet only)
     bool has_fuse = false;
     int top_k = MEMREAD_MAX_TOPK;          // rows per query of the memory read (PropagationNetwork(top_k=...), prop_net.py:141)
     float km = 0.f;                        // > 0: the kernelized read, standard deviation of its Gaussian (EvalMemoryReader(top_k, km), prop_net.py:75-99); 0: the plain read
@@ -94,6 +95,7 @@ private:
     Ev &push_pair(int cls, bool hbm);           // appends an event pair (from the pool, else created) to events
 };
 
+size_t wino_v_capacity(const Dims &d, int maxb);     // Work::wino_v_floats of a workspace whose largest conv batch is maxb
 // scratch for one in-flight frame computation (sized for nh x nw and k objects)
 struct Work {
     Dims d{};
@@ -179,8 +181,14 @@ int value_frame_parts(const Model &m, Work &w, hipStream_t s, const float *f16, 
 int decode(const Model &m, Work &w, hipStream_t s, const float *readout, const float *f16_thin,
            const float *s8, const float *s4, float *agg, long agg_stride, const float *dthin = nullptr,
            const float *cthin = nullptr, int G = 1, long slot_bs = 0, long agg_gs = 0);      // agg_gs: floats between the agg blocks of consecutive frames (0: (k + 1) * agg_stride)
+// the decoder alone, up to decoder.pred: w.logit4 [B][hw4] (decode = this + the sigmoid / aggregate tail)
+int decode_logit4(const Model &m, Work &w, hipStream_t s, const float *readout, const float *f16_thin, const float *s8, const float *s4,
+                  const float *dthin = nullptr, const float *cthin = nullptr, int G = 1, long slot_bs = 0);
 int fusion_logit(const Model &m, Work &w, hipStream_t s, const float *img4, const float *prev,
                  const float *curr, const float *attn2, float nc, float nr, float *logit);
+
+// capacity of the stage contexts' bank staging (stages.cpp) after growing `cap` to hold `need`: geometric, pure host code
+long stage_grow(long cap, long need);
 
 }  // namespace stcn
 

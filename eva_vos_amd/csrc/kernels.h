@@ -188,6 +188,10 @@ void upsample2x_add_launch(const float *x, const float *skip, float *u, int B, i
 // G > 1: G frames in one launch - frame g reads logit4 + g * logit_gs and writes agg + g * agg_gs
 void up4_sigmoid_aggregate_launch(const float *logit4, int k, int h4, int w4, float *agg,
                                   long agg_stride, hipStream_t s, long obj_stride = 0, int G = 1, long logit_gs = 0, long agg_gs = 0);
+// the same tail without the aggregation: logit4 [k,h4*w4] -> bilinear x4 -> sigmoid -> prob [k][nh*nw] (segment_with_query, prop_net.py:192)
+void up4_sigmoid_launch(const float *logit4, int k, int h4, int w4, float *prob, hipStream_t s);
+// aggregate_wbg (aggregate.py:22-37) on probabilities: prob [k][npix] -> out [k+1][npix] (keep_bg) or [k][npix]; hard: logits x 1000
+void aggregate_wbg_launch(const float *prob, int k, long npix, int keep_bg, int hard, float *out, hipStream_t s);
 // logits [k,npix] -> sigmoid -> aggregate -> agg rows (fusion output)
 void sigmoid_aggregate_launch(const float *logit, int k, long npix, float *agg, long agg_stride,
                               hipStream_t s);
@@ -207,6 +211,12 @@ void copy2_launch(const float *a, float *da, long na, const float *b, float *db,
 void interact_mask_launch(const float *mask, int mc, int H, int W, int nh, int nw, int lw, int lh,
                           float *prob_idx, long prob_row_stride, int kk, float *padded, float *pos,
                           float *neg, hipStream_t s);
+
+// ---------------------------------------------------------------- NCHW <-> rows (layout.hip)
+// B planes-tensors [C][ld] (R <= ld elements of every channel plane are read; ld: elements between channel planes) <-> B row-tensors [R][C];
+// batch element b at planes + b * planes_bs and rows + b * rows_bs.  C % 4 == 0; R, ld and the alignment of `planes` are free.
+void planes_to_rows_launch(const float *planes, long ld, long planes_bs, float *rows, long rows_bs, int B, int R, int C, hipStream_t s);
+void rows_to_planes_launch(const float *rows, long rows_bs, float *planes, long ld, long planes_bs, int B, int R, int C, hipStream_t s);
 
 // ---------------------------------------------------------------- CBAM (cbam.py:21-77)
 struct CbamW { const float *w1, *b1, *w2, *b2, *wsp; float bsp; };  // 512->32->512 MLP, 7x7 [2] conv

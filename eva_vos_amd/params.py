@@ -11,10 +11,16 @@ layout of the reference modules so the published checkpoints
   ``prop_net.py:13-30``; 405 tensors, 54 469 310 elements).
 * ``FusionNet``           <- reference ``mivos/model/fusion_net.py:8-30`` (12 tensors).
 
-There is deliberately no ``forward``: every computation on these weights is
+There is deliberately no torch ``forward``: every computation on these weights is
 done by the HIP engine (``csrc/``) which folds BatchNorm and repacks the
 tensors once per model.  The trees are built from a compact spec instead of
 hand-written module classes.
+
+The reference's inference-time stage calls are methods of the two classes:
+``PropagationNetwork.encode_key / encode_value / segment_with_query /
+get_attention`` and ``FusionNet.forward`` hand their tensors to the HIP
+kernels (``eva_vos_amd/stages.py``).  The training ``forward`` of the
+propagation network is not offered: calling the container raises.
 """
 from __future__ import annotations
 
@@ -155,6 +161,28 @@ class PropagationNetwork(_Bag):
         self.top_k = top_k
         self.km = km
 
+    # The reference's stage calls (prop_net.py:153-211) on fp32 CUDA tensors in the reference's shapes, batch 1, no autograd; the HIP
+    # kernels compute, torch only allocates the outputs (eva_vos_amd/stages.py).  ``top_k`` / ``km`` are read at every call.
+    def encode_key(self, frame):
+        """frame [1,3,nh,nw] (padded to multiples of 16) -> k16, f16_thin, f16, f8, f4 (prop_net.py:172-177)."""
+        from . import stages
+        return stages.encode_key(self, frame)
+
+    def encode_value(self, frame, kf16, masks):
+        """frame [1,3,nh,nw], kf16 [1,1024,h,w], masks [k,1,nh,nw] -> [k,512,1,h,w] (prop_net.py:153-170)."""
+        from . import stages
+        return stages.encode_value(self, frame, kf16, masks)
+
+    def segment_with_query(self, mk16, mv16, qf8, qf4, qk16, qv16):
+        """Memory read + decoder + sigmoid: per-object probabilities [k,1,nh,nw], not aggregated (prop_net.py:179-192)."""
+        from . import stages
+        return stages.segment_with_query(self, mk16, mv16, qf8, qf4, qk16, qv16)
+
+    def get_attention(self, mk16, pos_mask, neg_mask, qk16):
+        """mk16 [1,64,1,h,w], pos_mask / neg_mask [b,1,nh,nw], qk16 [1,64,h,w] -> [b,2,nh,nw] (prop_net.py:198-211)."""
+        from . import stages
+        return stages.get_attention(self, mk16, pos_mask, neg_mask, qk16)
+
 
 class FusionNet(_Bag):
     """Weights of the 6-conv fusion CNN (reference fusion_net.py:12-30)."""
@@ -164,3 +192,9 @@ class FusionNet(_Bag):
                          conv2=_seq(_conv(32, 32, 3), nn.Identity(), _conv(32, 32, 3)),
                          conv3=_seq(_conv(32, 32, 3), nn.Identity(), _conv(32, 32, 3)),
                          final_conv=_conv(32, 1, 3))
+
+    def forward(self, im, seg1, seg2, attn, time):
+        """The fusion logit [1,1,nh,nw] of one object (fusion_net.py:32-50) on the HIP kernels: fp32 CUDA tensors, batch 1, no autograd.
+        ``time`` [1,2] on the device costs one 8-byte blocking copy; as a CPU tensor it costs nothing."""
+        from . import stages
+        return stages.fusion_forward(self, im, seg1, seg2, attn, time)

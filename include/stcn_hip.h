@@ -154,6 +154,54 @@ int stcn_get_stats(const stcn_engine *e, stcn_stats *out);
 /* Algorithmic work of the last interact() in FLOP (2 x MAC of every conv / GEMM issued). */
 int stcn_get_flops(const stcn_engine *e, double *flops);
 
+/* ---- the reference's stage interface --------------------------------------------------------------------------
+ * What the reference's layer below InferenceCore offers: PropagationNetwork.encode_key / encode_value / segment_with_query / get_attention
+ * (model/propagation/prop_net.py:153-211), FusionNet.forward (model/fusion_net.py:32-50) and aggregate_wbg (model/aggregate.py:22-37), for
+ * callers that run their own propagation loop.  Every tensor is a device fp32 tensor in the REFERENCE's layout (NCHW, batch 1, C-contiguous
+ * unless a stride is given); the conversion to and from the engine's [rows][channels] happens on the device (csrc/layout.hip).
+ * A stage context holds the workspace of one frame size on one stream.  Stage calls enqueue on that stream and return; they never synchronise
+ * the device.  After the first call that reaches a given memory size (T, k) they do not allocate: the bank staging of stcn_stage_segment grows
+ * geometrically, and a growing call waits for the context's own stream once.  A context is NOT thread-safe; two streams take two contexts.
+ * Limits: batch 1, no autograd, 1 <= k <= STCN_MAX_OBJECTS, frames padded to multiples of 16 (tensor_util.py:62-80 - InferenceCore pads,
+ * inference_core.py:50-53), top_k / km as the model holds them. */
+typedef struct stcn_stage stcn_stage;
+/* nh, nw: the padded frame size, multiples of 16; max_objects: the largest k (and, + 1, the largest b of stcn_stage_attention) a call will
+ * pass, 1 .. STCN_MAX_OBJECTS; stream: hipStream_t (as void*), NULL = default stream.  The model outlives the context.
+ * Replaces: nothing the reference spells out - its modules allocate per call through torch's caching allocator. */
+int stcn_stage_create(const stcn_model *m, int nh, int nw, int max_objects, void *stream, stcn_stage **out);
+/* Waits for the context's stream, then hands its buffers back to the library's pool. */
+int stcn_stage_destroy(stcn_stage *s);
+/* PropagationNetwork.encode_key (prop_net.py:172-177).  frame [1,3,nh,nw] -> k16 [1,64,h16,w16], f16_thin [1,512,h16,w16],
+ * f16 [1,1024,h16,w16], f8 [1,512,h8,w8], f4 [1,256,h4,w4]; an output that is NULL is not written. */
+int stcn_stage_encode_key(stcn_stage *s, const float *frame, float *k16, float *f16_thin, float *f16, float *f8, float *f4);
+/* PropagationNetwork.encode_value (prop_net.py:153-170).  frame [1,3,nh,nw], kf16 [1,1024,h16,w16] (encode_key's f16), masks [k,1,nh,nw]
+ * (the "others" masks of :160-167 are formed inside) -> out [k,512,1,h16,w16]. */
+int stcn_stage_encode_value(stcn_stage *s, const float *frame, const float *kf16, const float *masks, int k, float *out);
+/* PropagationNetwork.segment_with_query (prop_net.py:179-192): memory read (EvalMemoryReader.get_affinity + readout, :80-115, with the
+ * model's top_k and km) + decoder + sigmoid -> prob [k,1,nh,nw], the per-object probabilities, NOT aggregated.
+ *   mk16 [1,64,T,h16,w16] with mk_plane_stride elements between its channel planes, mv16 [k,512,T,h16,w16] with mv_plane_stride between
+ *   channel planes and mv_object_stride between objects: the T-slices keys[:, :, :m_front] / values[:, :, :m_front] of preallocated banks
+ *   that do_pass hands over (inference_core.py:150-170) are read IN PLACE (plane strides Tm * h16 * w16 >= T * h16 * w16).
+ *   qf8 [1,512,h8,w8], qf4 [1,256,h4,w4], qk16 [1,64,h16,w16], qv16 [1,512,h16,w16] (encode_key's f16_thin).
+ * T * h16 * w16 < top_k returns STCN_E_INVALID (torch.topk raises there, prop_net.py:51-53). */
+int stcn_stage_segment(stcn_stage *s, const float *mk16, long mk_plane_stride, const float *mv16, long mv_plane_stride, long mv_object_stride,
+                       int T, int k, const float *qf8, const float *qf4, const float *qk16, const float *qv16, float *prob);
+/* PropagationNetwork.get_attention (prop_net.py:198-211; AttentionMemory :117-138 - a dense softmax, no top_k, no km).
+ * mk16 [1,64,1,h16,w16], pos / neg [b,1,nh,nw], qk16 [1,64,h16,w16] -> attn [b,2,nh,nw]; 1 <= b <= max_objects + 1. */
+int stcn_stage_attention(stcn_stage *s, const float *mk16, const float *pos, const float *neg, const float *qk16, int b, float *attn);
+/* FusionNet.forward (fusion_net.py:32-50) for one object.  im [1,3,nh,nw], seg1 / seg2 [1,1,nh,nw], attn [1,2,nh,nw], (nc, nr) = the two
+ * entries of `time` [1,2] (inference_core.py:199-201) -> logit [1,1,nh,nw].  STCN_E_STATE when the model has no fusion network. */
+int stcn_stage_fusion(stcn_stage *s, const float *im, const float *seg1, const float *seg2, const float *attn, float nc, float nr, float *logit);
+/* aggregate_wbg (model/aggregate.py:22-37).  prob [k,1,h,w] = [k][npix] -> out [k+1][npix] (keep_bg != 0) or [k][npix]; hard != 0: logits
+ * x 1000 (:30-32).  Needs no context: one launch on `stream`. */
+int stcn_aggregate_wbg(void *stream, const float *prob, int k, long npix, int keep_bg, int hard, float *out);
+/* A model of the FusionNet alone (fuse_net.to(device), inference_core.py:37, without a PropagationNetwork): it serves stcn_stage_fusion;
+ * every other stage call on a context of it, and stcn_engine_create, return STCN_E_STATE. */
+int stcn_fusion_model_create(int device, const stcn_weight_desc *fuse, int n_fuse, stcn_model **out);
+/* Test hook: the layout conversion of the stage calls alone.  to_rows != 0: src = B tensors [C][ld] (planes_bs apart), of which R <= ld
+ * elements per channel plane are read -> dst [B][R][C]; to_rows == 0: src [B][R][C] -> dst = B tensors [C][ld].  C % 4 == 0. */
+int stcn_test_transpose(void *stream, const float *src, float *dst, int B, int R, int C, long ld, long planes_bs, int to_rows);
+
 /* ---- stage-level hooks (used by tests/ and bench.py only; all pointers are device fp32) --------
  * Layouts are the engine's internal ones: activations NHWC, i.e. [rows = h*w][channels]. */
 
