@@ -69,6 +69,7 @@ PROTOTYPES = {
     "stcn_test_conv_trace": (_I, [_I]),
     "stcn_test_conv_trace_get": (C.c_char_p, []),
     "stcn_test_conv": (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 11),
+    "stcn_test_conv_ex": (_I, [_P, _P, _P, _P, _P, _P] + [_I] * 11 + [_P, _I, _L, _L, _L, _I, _L]),
     "stcn_test_conv_path": (_I, [_I] * 9 + [C.c_char_p, _I]),
     "stcn_test_conv_plan": (_I, [_I] * 9 + [C.POINTER(C.c_int32), _I, C.POINTER(_D)]),
     "stcn_test_sweep_plan": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int32), _I, C.POINTER(C.c_int32)]),
@@ -82,6 +83,7 @@ PROTOTYPES = {
     "stcn_bench_memory_read_km": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, C.POINTER(_F), C.POINTER(C.c_int32)]),
     "stcn_memread_plan": (_I, [_I, _I, C.POINTER(C.c_int32)]),
     "stcn_memread_scratch": (_I, [_I, C.POINTER(C.c_int64)]),
+    "stcn_test_kernel": (_I, [C.c_char_p, _P, C.POINTER(_P), _I, C.POINTER(C.c_int64), _I, C.POINTER(_D), _I]),
     "stcn_test_fail_at": (_I, [_I]),
     "stcn_test_side_delay_us": (_I, [_I]),
     "stcn_test_decode": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),

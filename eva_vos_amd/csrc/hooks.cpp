@@ -1,5 +1,6 @@
 // hooks.cpp - stage-level C-ABI entry points used by tests/ and bench.py (see include/stcn_hip.h).
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -117,22 +118,45 @@ void export_memread_plan(int N, int Q, int32_t *plan7) {
     const int32_t v[7] = {pl.steps, pl.ss, pl.ns, pl.nc1, pl.spc1, pl.nc2, pl.spc2};
     for (int i = 0; i < 7; ++i) plan7[i] = v[i];
 }
+// stcn_test_kernel: the kernels of kernels.h it reaches, with the argument counts include/stcn_hip.h documents
+struct SmallKernel { const char *name; int nptr, ni, nf; unsigned wide; };     // wide: bit i set = integer i is a long (a stride or an element count)
+const SmallKernel SMALL_KERNELS[] = {
+    {"maxpool3x3s2", 2, 4, 0, 0}, {"upsample2x_add", 3, 6, 0, 1u << 4}, {"up4_sigmoid_aggregate", 2, 8, 0, 1u << 3 | 1u << 4 | 1u << 6 | 1u << 7},
+    {"up4_sigmoid", 2, 3, 0, 0}, {"sigmoid_aggregate", 2, 3, 0, 1u << 1 | 1u << 2}, {"argmax", 2, 3, 0, 1u << 2}, {"rowsumsq", 2, 5, 0, 1u << 3 | 1u << 4},
+    {"pack_image", 2, 6, 0, 0}, {"pack_value_input", 3, 3, 0, 1u << 0}, {"pack_fusion_input", 5, 1, 2, 1u << 0}, {"interact_mask", 5, 9, 0, 1u << 7},
+    {"cbam", 7, 3, 1, 0}, {"copy_rows", 2, 4, 0, 1u << 0 | 1u << 1 | 1u << 3}, {"copy2", 4, 2, 0, 1u << 0 | 1u << 1}, {"fill", 1, 1, 1, 1u << 0},
+};
 }  // namespace
 
 extern "C" {
 
 int stcn_test_conv(void *stream, const float *x, const float *wgt, const float *bias, const float *res, float *y, int B,
                    int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int flags, int splitk) {
-    if (Cin % 4 || pad != KH / 2 || KH != KW) { set_error("stcn_test_conv: Cin%%4==0, square kernel, pad=K/2 required"); return STCN_E_INVALID; }
+    return stcn_test_conv_ex(stream, x, wgt, bias, res, y, B, H, W, Cin, Cout, KH, KW, stride, pad, flags, splitk, nullptr, 0, CONV_DENSE, CONV_DENSE,
+                             CONV_DENSE, 0, CONV_DENSE);
+}
+
+// The one rig of the conv hooks: the operands in every form ConvArgs takes (a second source, batch strides of the input, the residual and
+// the output, the per-frame residual of a batch laid out [object][frame]).  plan_conv's own refusals pass through with its message.
+int stcn_test_conv_ex(void *stream, const float *x, const float *wgt, const float *bias, const float *res, float *y, int B,
+                      int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int flags, int splitk,
+                      const float *x1, int c1, long bs0, long bs1, long res_bs, int res_bmod, long y_bs) {
+    if (!x || !wgt || !y || B < 1 || H < 1 || W < 1 || Cin < 4 || Cout < 1 || stride < 1 || Cin % 4 || pad != KH / 2 || KH != KW) {
+        set_error("stcn_test_conv_ex: x, w and y, B, H, W, Cout, stride >= 1, Cin%%4==0, square kernel, pad=K/2 required"); return STCN_E_INVALID;
+    }
+    if ((x1 != nullptr) != (c1 > 0) || c1 % 4 || bs0 < CONV_DENSE || bs1 < CONV_DENSE || res_bs < CONV_DENSE || res_bmod < 0 || y_bs < CONV_DENSE) {
+        set_error("stcn_test_conv_ex: a second source has c1 > 0 channels (c1%%4==0); strides are -1 (dense), 0 (broadcast) or elements; res_bmod >= 0");
+        return STCN_E_INVALID;
+    }
     hipStream_t s = (hipStream_t)stream;
-    ConvW cw = test_convw(Cin, Cout, KH, KW);
+    ConvW cw = test_convw(Cin + c1, Cout, KH, KW);
     DevBuf wpad;
     RC(wpad.alloc((size_t)Cout * cw.Kp));
     HIPCHK(hipMemsetAsync(wpad.p, 0, (size_t)Cout * cw.Kp * 4, s));
     HIPCHK(hipMemcpy2DAsync(wpad.p, (size_t)cw.Kp * 4, wgt, (size_t)cw.K * 4, (size_t)cw.K * 4, Cout, hipMemcpyDeviceToDevice, s));
     cw.w = wpad.p; cw.bias = const_cast<float *>(bias);
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    const bool wino = KH == 3 && stride == 1;          // stride-1 3x3: the Winograd path, as in the engine
+    const bool wino = KH == 3 && stride == 1 && !x1;   // stride-1 3x3 of one source: the Winograd path, as in the engine
     std::vector<float> hw;
     if (wino) {
         HIPCHK(hipStreamSynchronize(s));
@@ -143,13 +167,15 @@ int stcn_test_conv(void *stream, const float *x, const float *wgt, const float *
     RC(r.init(cw, wino ? &hw : nullptr, flags & 4, B, OH, OW, (size_t)16 * 1024 * 1024));    // flags bit 2: as a decoder layer (F(4x4,3x3))
     if (wino && (flags & 4)) r.m.wino4_min_wg = 0;
     if (Cout == 1) {
-        if (stride != 1) { set_error("Cout==1 path is stride 1"); return STCN_E_INVALID; }
+        const bool dense = !x1 && bs0 == CONV_DENSE && y_bs == CONV_DENSE && !res;
+        if (stride != 1 || !dense) { set_error("Cout==1 path is stride 1, one dense source, dense output, no residual"); return STCN_E_INVALID; }
         float b0 = 0.f;
         if (bias) HIPCHK(hipMemcpy(&b0, bias, 4, hipMemcpyDeviceToHost));
         conv_n1_launch(x, wpad.p, b0, y, B, H, W, Cin, KH, flags & 1, s);
         set_conv_path("n1");
     } else {
-        RC(run_conv(r.m, r.w, s, "t", ConvArgs(x, Cin, B, H, W).strided(stride).out(y).residual(res).relu(flags & 1, (flags >> 1) & 1).splitk(splitk)));
+        RC(run_conv(r.m, r.w, s, "t", ConvArgs(x, Cin, B, H, W, bs0).concat(x1, c1, x1 ? bs1 : 0).strided(stride).out(y, y_bs == CONV_DENSE ? 0 : y_bs)
+                                          .residual(res, res_bs, res_bmod).relu(flags & 1, (flags >> 1) & 1).splitk(splitk)));
     }
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
@@ -455,6 +481,80 @@ int stcn_bench_mfma_rate(void *stream, int ms_target, float *tflops, float *ms_o
     HIPCHK(hipGetLastError());
     *tflops = (float)(fl / (ms * 1e-3) / 1e12);
     if (ms_out) *ms_out = ms;
+    return STCN_OK;
+}
+
+// One launch of a small kernel by name (include/stcn_hip.h lists the arguments of each).  Names and counts are checked before any device call.
+int stcn_test_kernel(const char *name, void *stream, void *const *ptrs, int nptr, const int64_t *iv, int ni, const double *fv, int nf) {
+    const SmallKernel *k = nullptr;
+    for (const SmallKernel &c : SMALL_KERNELS)
+        if (name && !strcmp(name, c.name)) k = &c;
+    if (!k) { set_error("stcn_test_kernel: unknown kernel '%s'", name ? name : "(null)"); return STCN_E_INVALID; }
+    bool ok = nptr == k->nptr && ni == k->ni && nf == k->nf && ptrs && iv && (nf == 0 || fv);
+    for (int i = 0; ok && i < nptr; ++i) ok = ptrs[i] != nullptr;
+    for (int i = 0; ok && i < ni; ++i) ok = iv[i] >= 0 && iv[i] <= ((k->wide >> i) & 1 ? (1LL << 40) : (long long)INT_MAX);      // the int parameters are not narrowed
+    if (!ok) {
+        set_error("stcn_test_kernel: '%s' takes %d non-null pointers, %d non-negative integers and %d doubles (got %d, %d, %d); sizes fit an int, strides 2^40",
+                  k->name, k->nptr, k->ni, k->nf, nptr, ni, nf);
+        return STCN_E_INVALID;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const std::string n = k->name;
+    auto F = [&](int i) { return static_cast<float *>(ptrs[i]); };
+    auto I = [&](int i) { return (int)iv[i]; };
+    // the sizes the kernels take on trust: object counts within the register arrays, channel counts in whole 16-byte accesses
+    auto objects = [&](int64_t v) { return v >= 1 && v <= STCN_MAX_OBJECTS; };
+    auto bad = [&](const char *what) { set_error("stcn_test_kernel: '%s' needs %s", k->name, what); return STCN_E_INVALID; };
+    DevBuf scratch;
+    if (n == "maxpool3x3s2") {
+        if (iv[3] % 4 || iv[3] < 4 || iv[1] < 2 || iv[2] < 2 || iv[0] < 1) return bad("B >= 1, H, W >= 2, C % 4 == 0");
+        maxpool3x3s2_launch(F(0), F(1), I(0), I(1), I(2), I(3), s);
+    } else if (n == "upsample2x_add") {
+        if (iv[3] % 4 || iv[3] < 4 || iv[0] < 1 || iv[1] < 1 || iv[2] < 1) return bad("B, h, w >= 1, C % 4 == 0");
+        upsample2x_add_launch(F(0), F(1), F(2), I(0), I(1), I(2), I(3), s, (long)iv[4], I(5));
+    } else if (n == "up4_sigmoid_aggregate") {
+        if (!objects(iv[0]) || iv[1] < 1 || iv[2] < 1 || iv[5] < 1) return bad("1 <= k <= STCN_MAX_OBJECTS, h4, w4, G >= 1");
+        up4_sigmoid_aggregate_launch(F(0), I(0), I(1), I(2), F(1), (long)iv[3], s, (long)iv[4], I(5), (long)iv[6], (long)iv[7]);
+    } else if (n == "up4_sigmoid") {
+        if (!objects(iv[0]) || iv[1] < 1 || iv[2] < 1) return bad("1 <= k <= STCN_MAX_OBJECTS, h4, w4 >= 1");
+        up4_sigmoid_launch(F(0), I(0), I(1), I(2), F(1), s);
+    } else if (n == "sigmoid_aggregate") {
+        if (!objects(iv[0]) || iv[1] < 1) return bad("1 <= k <= STCN_MAX_OBJECTS, npix >= 1");
+        sigmoid_aggregate_launch(F(0), I(0), (long)iv[1], F(1), (long)iv[2], s);
+    } else if (n == "argmax") {
+        if (iv[0] < 1 || iv[0] > 256 || iv[1] < 1 || iv[2] < 1) return bad("1 <= kk <= 256 (uint8 masks), T, npix >= 1");
+        argmax_launch(F(0), I(0), I(1), (long)iv[2], static_cast<uint8_t *>(ptrs[1]), s);
+    } else if (n == "rowsumsq") {
+        if (iv[0] < 1 || iv[1] % 4 || iv[1] < 4 || iv[2] < 1) return bad("n, B >= 1, C % 4 == 0");
+        rowsumsq_launch(F(0), I(0), I(1), F(1), s, I(2), (long)iv[3], (long)iv[4]);
+    } else if (n == "pack_image") {
+        if (iv[0] < 1 || iv[1] < 1 || iv[4] + iv[1] > iv[3] || iv[5] + iv[0] > iv[2]) return bad("H, W >= 1, lh + H <= nh, lw + W <= nw");
+        pack_image_launch(F(0), F(1), I(0), I(1), I(2), I(3), I(4), I(5), s);
+    } else if (n == "pack_value_input") {
+        if (!objects(iv[1]) || iv[2] < 1) return bad("1 <= k <= STCN_MAX_OBJECTS, npix >= 1");
+        pack_value_input_launch(F(0), F(1), (long)iv[0], I(1), I(2), F(2), s);
+    } else if (n == "pack_fusion_input") {
+        if (iv[0] < 1) return bad("npix >= 1");
+        pack_fusion_input_launch(F(0), F(1), F(2), F(3), (float)fv[0], (float)fv[1], (long)iv[0], F(4), s);
+    } else if (n == "interact_mask") {
+        if (iv[8] < 1 || (iv[0] != 1 && iv[0] != iv[8]) || iv[1] < 1 || iv[2] < 1 || iv[6] + iv[1] > iv[3] || iv[5] + iv[2] > iv[4])
+            return bad("kk >= 1, mc 1 or kk, H, W >= 1, lh + H <= nh, lw + W <= nw");
+        interact_mask_launch(F(0), I(0), I(1), I(2), I(3), I(4), I(5), I(6), F(1), (long)iv[7], I(8), F(2), F(3), F(4), s);
+    } else if (n == "cbam") {
+        if (iv[0] < 1 || iv[1] < 1 || iv[2] < 1) return bad("B, h, w >= 1");
+        RC(scratch.alloc((size_t)iv[0] * (16 * 1024 + 512 + 2 * (size_t)(iv[1] * iv[2]))));      // the size kernels.h states
+        cbam_launch(F(0), F(1), I(0), I(1), I(2), CbamW{F(2), F(3), F(4), F(5), F(6), (float)fv[0]}, scratch.p, s);
+    } else if (n == "copy_rows") {
+        if (iv[2] < 1 || iv[3] < 1) return bad("rows, n >= 1");
+        copy_rows_launch(F(0), (long)iv[0], F(1), (long)iv[1], I(2), (long)iv[3], s);
+    } else if (n == "copy2") {
+        if (iv[0] % 4) return bad("na % 4 == 0");
+        copy2_launch(F(0), F(1), (long)iv[0], F(2), F(3), (long)iv[1], s);
+    } else {
+        fill_launch(F(0), (float)fv[0], (long)iv[0], s);
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipGetLastError());
     return STCN_OK;
 }
 

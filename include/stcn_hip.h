@@ -208,10 +208,22 @@ int stcn_test_transpose(void *stream, const float *src, float *dst, int B, int R
 /* Generic convolution through the implicit-GEMM kernel (what every nn.Conv2d of the path lowers to:
  * modules.py / mod_resnet.py / prop_net.py convs).  x: [B,H,W,Cin] (Cin multiple of 4),
  * w: [Cout,KH,KW,Cin], bias: [Cout], res: [B,OH,OW,Cout] or NULL, y: [B,OH,OW,Cout].
- * flags: bit0 relu on input, bit1 relu on output.  splitk<=0 lets the engine choose. */
+ * flags: bit0 relu on input, bit1 relu on output.  splitk<=0 lets the engine choose.  Cout == 1 (the dot-product kernel of decoder.pred)
+ * is stride 1 and takes no residual: res must be NULL there (STCN_E_INVALID otherwise; it used to be ignored). */
 int stcn_test_conv(void *stream, const float *x, const float *w, const float *bias, const float *res,
                    float *y, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                    int pad, int flags, int splitk);
+
+/* The same convolution with its operands in every form the engine passes (stcn_test_conv is this call with the dense defaults).  Cin: channels
+ * of x; x1 / c1: a second source whose channels follow those of x (NULL / 0: one source) - w stays [Cout][KH*KW*(Cin + c1)], ordered (kh, kw,
+ * cin) with the channels of x first.  Batch strides in elements: -1 = dense, 0 = broadcast (one image serves every batch element; y_bs has no
+ * broadcast: 0 is dense too).  bs0, bs1: of x and x1; res_bs: of res; res_bmod > 0: batch element b adds res + (b % res_bmod) * res_bs (a
+ * per-frame residual under a batch laid out [object][frame]); y_bs: of y.  The caller allocates every buffer to the extent its stride implies:
+ * B * stride floats, or one image when the stride is 0.  What the planner refuses (a two-source input whose Cin is no multiple of 32, an
+ * operand beyond 2 GiB) returns STCN_E_INVALID with its message before anything is launched. */
+int stcn_test_conv_ex(void *stream, const float *x, const float *w, const float *bias, const float *res,
+                      float *y, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                      int pad, int flags, int splitk, const float *x1, int c1, long bs0, long bs1, long res_bs, int res_bmod, long y_bs);
 
 /* Test hook: the kernel family and plan stcn_test_conv would run this shape as (the string stcn_last_conv_path() gives after it), from
  * the host-side planners alone: nothing is allocated on a device, nothing is launched, no GPU is needed.  out: n bytes. */
@@ -239,6 +251,29 @@ int stcn_test_sweep_plan(int idx, int closest, int mem_freq, int cap, int32_t *o
  * Lets a sequence test assert that e.g. every decoder layer of a 853x480 clip really ran as "wino4 ...". */
 int stcn_test_conv_trace(int on);
 const char *stcn_test_conv_trace_get(void);
+
+/* Test hook: ONE launch of a small kernel (elementwise / pooling / CBAM, csrc/kernels.h) by name, then a synchronisation.  ptrs: nptr device
+ * pointers, iv: ni non-negative integers (sizes, strides in elements), fv: nf doubles, per kernel in this order (layouts as kernels.h states):
+ *   maxpool3x3s2          ptrs x, y                           iv B, H, W, C
+ *   upsample2x_add        ptrs x, skip, u                     iv B, h, w, C, skip_bs, skip_bmod
+ *   up4_sigmoid_aggregate ptrs logit4, agg                    iv k, h4, w4, agg_stride, obj_stride, G, logit_gs, agg_gs
+ *   up4_sigmoid           ptrs logit4, prob                   iv k, h4, w4
+ *   sigmoid_aggregate     ptrs logit, agg                     iv k, npix, agg_stride
+ *   argmax                ptrs prob, masks (uint8)            iv kk, T, npix
+ *   rowsumsq              ptrs x, out                         iv n, C, B, x_bs, out_bs
+ *   pack_image            ptrs img_chw, out                   iv H, W, nh, nw, lw, lh
+ *   pack_value_input      ptrs img4, masks, out               iv mask_stride, k, npix
+ *   pack_fusion_input     ptrs img4, prev, curr, attn2, out   iv npix                                  fv nc, nr
+ *   interact_mask         ptrs mask, prob_idx, padded, pos, neg   iv mc, H, W, nh, nw, lw, lh, prob_row_stride, kk
+ *   cbam                  ptrs x, out, w1, b1, w2, b2, wsp    iv B, h, w                               fv bsp   (the hook allocates the scratch)
+ *   copy_rows             ptrs src, dst                       iv src_stride, dst_stride, rows, n
+ *   copy2                 ptrs a, da, b, db                   iv na, nb
+ *   fill                  ptrs p                              iv n                                     fv v
+ * Strides and element counts (skip_bs, agg_stride, obj_stride, logit_gs, agg_gs, x_bs, out_bs, mask_stride, prob_row_stride, src_stride,
+ * dst_stride, the npix of sigmoid_aggregate / argmax / pack_fusion_input, n of copy_rows / fill, na, nb) may reach 2^40, every other integer INT_MAX.
+ * An unknown name, other counts than these, a null pointer, a negative integer or one beyond its range return STCN_E_INVALID - the message names the kernel and
+ * the counts it takes - before any device call. */
+int stcn_test_kernel(const char *name, void *stream, void *const *ptrs, int nptr, const int64_t *iv, int ni, const double *fv, int nf);
 
 /* encode_key of one frame (prop_net.py:172-177).  img: [1,3,nh,nw] NCHW padded.  Outputs (NHWC):
  * k16 [hw16,64], f16_thin [hw16,512], f16 [hw16,1024], f8 [hw8,512], f4 [hw4,256]; any may be NULL. */

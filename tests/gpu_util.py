@@ -2,6 +2,7 @@
 import ctypes as C
 
 import torch
+import torch.nn.functional as F
 
 from eva_vos_amd import _lib
 from eva_vos_amd.inference_core import _model_for
@@ -42,3 +43,33 @@ def call(name, *args):
     _lib.check(getattr(_lib.lib(), name)(*conv), name)
     torch.cuda.synchronize()
     del keep
+
+
+def kernel(name, ptrs, iv, fv=()):
+    """stcn_test_kernel: one launch of a small kernel by name (argument order: include/stcn_hip.h); ptrs are device tensors."""
+    pa = (C.c_void_p * max(1, len(ptrs)))(*[t.data_ptr() for t in ptrs])
+    ia = (C.c_int64 * max(1, len(iv)))(*[int(v) for v in iv])
+    fa = (C.c_double * max(1, len(fv)))(*[float(v) for v in fv])
+    _lib.check(_lib.lib().stcn_test_kernel(name.encode(), stream(), pa, len(ptrs), ia, len(iv), fa, len(fv)), name)
+    torch.cuda.synchronize()
+
+
+def guarded(n, dtype=torch.float32, guard=64):
+    """A NaN-filled (uint8: 0xFF) device buffer of n elements in front of `guard` more that a kernel must leave alone."""
+    if dtype == torch.uint8:
+        return torch.full((n + guard,), 255, dtype=torch.uint8, device="cuda")
+    return torch.full((n + guard,), float("nan"), dtype=dtype, device="cuda")
+
+
+def guard_intact(buf, n):
+    tail = buf[n:]
+    return bool((tail == 255).all()) if buf.dtype == torch.uint8 else bool(torch.isnan(tail).all())
+
+
+def torch_aggregate_wbg(prob, keep_bg=False, hard=False):
+    """model/aggregate.py:22-37, in the precision of `prob`."""
+    new_prob = torch.cat([torch.prod(1 - prob, dim=0, keepdim=True), prob], 0).clamp(1e-7, 1 - 1e-7)
+    logits = torch.log((new_prob / (1 - new_prob)))
+    if hard:
+        logits = logits * 1000
+    return F.softmax(logits, dim=0) if keep_bg else F.softmax(logits, dim=0)[1:]

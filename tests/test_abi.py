@@ -35,6 +35,41 @@ def test_null_arguments_are_rejected_without_touching_the_gpu():
     assert lib.stcn_model_destroy(None) == 0 and lib.stcn_engine_destroy(None) == 0
 
 
+def documented_small_kernels():
+    """name -> (pointers, integers, doubles) as the comment above stcn_test_kernel in the header lists them: 'name  ptrs a, b  iv c, d  fv e'."""
+    src = open(os.path.join(ROOT, "include", "stcn_hip.h")).read()
+    out = {}
+    for name, ptrs, iv, fv in re.findall(r"^ \*   (\w+)\s+ptrs ([\w, ()]+?)\s+iv ([\w, ]+?)(?:\s+fv ([\w, ]+?))?(?:\s+\(.*\))?$", src, flags=re.M):
+        count = lambda t: len([x for x in re.sub(r"\(.*?\)", "", t).split(",") if x.strip()])
+        out[name] = (count(ptrs), count(iv), count(fv) if fv else 0)
+    return out
+
+
+def test_small_kernel_hook_rejects_unknown_names_and_wrong_counts_before_any_device_call():
+    """stcn_test_kernel checks the name and the argument counts on the host: on a machine without a GPU both fail with STCN_E_INVALID and
+    a message that names the kernel and the counts it takes - never with a HIP error.  The counts are read from the header's table, so the
+    documented argument lists and the dispatcher's cannot drift apart; an int-typed size beyond INT_MAX is refused, a stride is not narrowed."""
+    import ctypes as C
+    lib = _lib.lib()
+    ptrs, iv, fv = (C.c_void_p * 8)(*([1] * 8)), (C.c_int64 * 9)(*([1] * 9)), (C.c_double * 2)(0.0, 0.0)
+    assert lib.stcn_test_kernel(b"no_such_kernel", None, ptrs, 2, iv, 4, fv, 0) == -1
+    assert b"unknown kernel 'no_such_kernel'" in lib.stcn_last_error()
+    assert lib.stcn_test_kernel(None, None, ptrs, 2, iv, 4, fv, 0) == -1
+    for name, counts in documented_small_kernels().items():
+        for off in ((1, 0, 0), (0, 1, 0), (0, 0, 1)):
+            got = [c + o for c, o in zip(counts, off)]
+            assert lib.stcn_test_kernel(name.encode(), None, ptrs, got[0], iv, got[1], fv, got[2]) == -1, name
+            msg = lib.stcn_last_error().decode()
+            assert f"'{name}' takes {counts[0]} non-null pointers, {counts[1]} non-negative integers and {counts[2]} doubles" in msg, msg
+    null = (C.c_void_p * 2)(1, None)
+    assert lib.stcn_test_kernel(b"maxpool3x3s2", None, null, 2, iv, 4, fv, 0) == -1 and b"'maxpool3x3s2' takes 2" in lib.stcn_last_error()
+    assert len(documented_small_kernels()) == 15
+    big = (C.c_int64 * 4)(1, 2, 1 << 31, 4)
+    assert lib.stcn_test_kernel(b"maxpool3x3s2", None, ptrs, 2, big, 4, fv, 0) == -1 and b"'maxpool3x3s2' takes 2" in lib.stcn_last_error()
+    neg = (C.c_int64 * 4)(1, 2, -2, 4)
+    assert lib.stcn_test_kernel(b"maxpool3x3s2", None, ptrs, 2, neg, 4, fv, 0) == -1 and b"'maxpool3x3s2' takes 2" in lib.stcn_last_error()
+
+
 def test_state_dict_layout():
     p, f = PropagationNetwork(), FusionNet()
     sd = p.state_dict()

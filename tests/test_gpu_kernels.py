@@ -75,6 +75,9 @@ CONVS = [
     (2, 19, 21, 256, 192, 1, 1, 2, 0),
     (1, 30, 54, 512, 128, 1, 1, 0, 3),
     (2, 30, 54, 256, 512, 1, 2, 2, 0),
+    # Cout 1 over a batch (the decoder runs decoder.pred at B = frames x objects): strips that cross image boundaries
+    (6, 9, 70, 256, 1, 3, 1, 1, 0),
+    (3, 21, 150, 32, 1, 3, 1, 0, 0),
 ]
 
 
@@ -92,6 +95,7 @@ PATHS = [
     "wino4 chunks=1 +tail", "wino4 chunks=1 +tail", "wino4 chunks=1 +tail", "wino4 chunks=1 +tail",
     "wino4", "wino4", "wino4",
     "direct_pointwise", "direct_pointwise splitk=3", "direct splitk",
+    "n1", "n1",
 ]
 
 

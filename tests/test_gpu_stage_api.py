@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from conftest import load_golden, rel_err, sample_of
 from eva_vos_amd import _lib, synth
 from eva_vos_amd.params import PropagationNetwork
+from gpu_util import torch_aggregate_wbg
 from oracle import stcn_oracle as O
 from test_oracle_golden import check_sequence_against_golden, run_sequence
 
@@ -136,15 +137,6 @@ def test_get_attention_matches_the_oracle(tag, nets, weights):
     d = float((out.cpu() - ref).abs().max())
     print(f"{tag} get_attention: max |d| vs oracle {d:.2e}")
     assert d < 1e-5
-
-
-def torch_aggregate_wbg(prob, keep_bg=False, hard=False):
-    """model/aggregate.py:22-37, in the precision of `prob`."""
-    new_prob = torch.cat([torch.prod(1 - prob, dim=0, keepdim=True), prob], 0).clamp(1e-7, 1 - 1e-7)
-    logits = torch.log((new_prob / (1 - new_prob)))
-    if hard:
-        logits = logits * 1000
-    return F.softmax(logits, dim=0) if keep_bg else F.softmax(logits, dim=0)[1:]
 
 
 @pytest.mark.parametrize("k", [1, 3, 32])
