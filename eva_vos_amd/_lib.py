@@ -92,6 +92,10 @@ PROTOTYPES = {
     "stcn_metrics_jf_counts": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "stcn_metrics_j_counts": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "stcn_metrics_round": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P]),
+    "stcn_metrics_objects_scratch": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int64)]),
+    "stcn_metrics_objects_jf_counts": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "stcn_metrics_objects_j_counts": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "stcn_metrics_objects_round": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
     "stcn_bench_conv": (_I, [_P] + [_I] * 11 + [C.POINTER(_F), C.POINTER(_D)]),
     "stcn_bench_mfma_rate": (_I, [_P, _I, C.POINTER(_F), C.POINTER(_F)]),
     "stcn_pool_release": (_I, []),

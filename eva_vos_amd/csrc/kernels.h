@@ -291,6 +291,20 @@ void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, co
                         int Tn, int H, int W, int radius, double no_object, uint8_t *gen, uint8_t *bmap, int *counts, int T_all, double *quality,
                         int *select, hipStream_t s, int t0);
 
+// ---- the same for LABEL MAPS of k objects (0 = background, o in 1..k = object o; a label above k counts as background) ----
+// counts [k][T_all][6]: per object the six integers jf_counts_launch gives for the binary masks (gt == o), (pred == o).  The boundary scratch
+// holds per pixel the SET of objects the pixel is a boundary pixel of, one word for the gt map and one for the pred map, bit o - 1 = object o:
+// bytes for k <= 8, 32-bit words above.  label_scratch_bytes is the one statement of its size.
+size_t label_scratch_bytes(int k, int T, int H, int W);
+// gt / pred / bsets / counts point at the first of the Tn frames to count; T_all = frames per object in counts (the object stride)
+void label_counts_launch(const uint8_t *gt, const uint8_t *pred, int k, int Tn, int H, int W, int radius, void *bsets, int *counts, int T_all,
+                         hipStream_t s);
+// a k-object annotation round: compose, counts, per-object quality [k][T_all], frame quality [T_all] (mean over the objects present in the
+// ground truth of the frame, ascending o) and its arg-min; pointer conventions as round_score_launch, present = uint8 [k][T_all]
+void label_round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated,
+                              const uint8_t *present, int k, int Tn, int H, int W, int radius, double no_object, uint8_t *gen, void *bsets,
+                              int *counts, int T_all, double *object_quality, double *quality, int *select, hipStream_t s, int t0);
+
 // pure fp32-MFMA load (no memory traffic): launches `grid` workgroups of 12 waves x iters x 12 MFMAs, returns the FLOP of the launch
 double mfma_probe_launch(float *out, int grid, int iters, hipStream_t s);
 

@@ -147,31 +147,24 @@ __global__ __launch_bounds__(256) void round_compose_kernel(const uint8_t *__res
 // reference's special cases, J&F = 0.5 (J + F); frames whose ground truth is empty get the NO_OBJECT token.  IEEE division / multiplication /
 // addition are correctly rounded on the device as on the host, so the values - and therefore the arg-min (first index of the minimum, as
 // numpy.argmin) - are bit-identical to the host path's.  One workgroup; T <= a few hundred.
-__global__ __launch_bounds__(256) void round_quality_kernel(const int *__restrict__ counts, const uint8_t *__restrict__ noobj, int T, int j_only,
-                                                            double no_object, double *__restrict__ quality, int *__restrict__ select) {
+__device__ __forceinline__ double quality_of(const int *__restrict__ c, int j_only) {
+    const double j = c[1] == 0 ? 0.0 : __ddiv_rn((double)c[0], (double)c[1]);
+    if (j_only) return j;
+    const int n_gt = c[2], n_fg = c[3];
+    double p, r;
+    if (n_fg == 0 && n_gt > 0) { p = 1.0; r = 0.0; }
+    else if (n_fg > 0 && n_gt == 0) { p = 0.0; r = 1.0; }
+    else if (n_fg == 0 && n_gt == 0) { p = 1.0; r = 1.0; }
+    else { p = __ddiv_rn((double)c[5], (double)n_fg); r = __ddiv_rn((double)c[4], (double)n_gt); }
+    const double s = __dadd_rn(p, r);
+    const double f = s == 0.0 ? 0.0 : __ddiv_rn(__dmul_rn(__dmul_rn(2.0, p), r), s);
+    return __dmul_rn(0.5, __dadd_rn(j, f));
+}
+
+// first index of the minimum over the workgroup's 256 (best, besti) pairs, each the first minimum of its thread's ascending subsequence
+__device__ __forceinline__ void block_argmin(double best, int besti, int *__restrict__ select) {
     __shared__ double sv[256];
     __shared__ int si[256];
-    double best = __builtin_inf();
-    int besti = 0x7fffffff;
-    for (int t = threadIdx.x; t < T; t += 256) {
-        const int *c = counts + t * 6;
-        const double j = c[1] == 0 ? 0.0 : __ddiv_rn((double)c[0], (double)c[1]);
-        double q = j;
-        if (!j_only) {
-            const int n_gt = c[2], n_fg = c[3];
-            double p, r;
-            if (n_fg == 0 && n_gt > 0) { p = 1.0; r = 0.0; }
-            else if (n_fg > 0 && n_gt == 0) { p = 0.0; r = 1.0; }
-            else if (n_fg == 0 && n_gt == 0) { p = 1.0; r = 1.0; }
-            else { p = __ddiv_rn((double)c[5], (double)n_fg); r = __ddiv_rn((double)c[4], (double)n_gt); }
-            const double s = __dadd_rn(p, r);
-            const double f = s == 0.0 ? 0.0 : __ddiv_rn(__dmul_rn(__dmul_rn(2.0, p), r), s);
-            q = __dmul_rn(0.5, __dadd_rn(j, f));
-        }
-        if (noobj[t]) q = no_object;
-        quality[t] = q;
-        if (q < best) { best = q; besti = t; }                               // ascending t per thread: the first minimum of its subsequence
-    }
     sv[threadIdx.x] = best; si[threadIdx.x] = besti;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -182,6 +175,19 @@ __global__ __launch_bounds__(256) void round_quality_kernel(const int *__restric
         __syncthreads();
     }
     if (threadIdx.x == 0) select[0] = si[0];
+}
+
+__global__ __launch_bounds__(256) void round_quality_kernel(const int *__restrict__ counts, const uint8_t *__restrict__ noobj, int T, int j_only,
+                                                            double no_object, double *__restrict__ quality, int *__restrict__ select) {
+    double best = __builtin_inf();
+    int besti = 0x7fffffff;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        double q = quality_of(counts + t * 6, j_only);
+        if (noobj[t]) q = no_object;
+        quality[t] = q;
+        if (q < best) { best = q; besti = t; }                               // ascending t per thread: the first minimum of its subsequence
+    }
+    block_argmin(best, besti, select);
 }
 
 // masks / gt / annotated / gen / counts point at the FIRST of the Tn frames to (re)compose and count; the quality and the arg-min cover all
@@ -205,6 +211,201 @@ void jf_counts_launch(const uint8_t *gt, const uint8_t *pred, int T, int H, int 
     // radius < 0: J only (intersection / union; bmap may be null)
     hipLaunchKernelGGL(jf_boundary_kernel, dim3(blocks), dim3(256), 0, s, gt, pred, T, H, W, bmap, counts, radius < 0 ? 1 : 0);
     if (radius >= 0) hipLaunchKernelGGL(jf_match_kernel, dim3(blocks), dim3(256), 0, s, bmap, T, H, W, radius, counts);
+}
+
+// ---- label maps of k objects: one pass over the pixels serves every object ------------------------------------------------------------
+// A pixel carries ONE label per map, so it touches the region counters of at most two objects (its gt label, its pred label) and is a
+// boundary pixel of at most four per map (its own label and those of its east / south / south-east neighbours, wherever they differ:
+// object o's binary mask changes between two pixels exactly when one of them is o and the other is not).  The boundary pass stores, per
+// pixel and map, the SET of those objects (BSet: bit o - 1 = object o; background takes part only as "not o"); the match pass scans the
+// disk once per boundary pixel and ORs the sets it finds - object o's gt boundary is matched iff bit o - 1 is in the OR of the pred sets,
+// so a neighbouring object's boundary inside the disk never counts.  Per object this is the arithmetic of the binary kernels above.
+// Counters: a wave that lies inside one frame adds into its own [k][6] table in LDS (integer LDS atomics) and the workgroup flushes the
+// non-zero entries with one global integer atomic each; a wave across a frame boundary adds per pixel to global memory, as above.
+static constexpr int LT = STCN_MAX_OBJECTS * 6;          // the C entry points refuse more objects
+static_assert(STCN_MAX_OBJECTS <= 32, "a pixel's object set is at most one 32-bit word");
+
+template <typename Wd> struct alignas(2 * sizeof(Wd)) BSet { Wd g, p; };
+
+__device__ __forceinline__ int label_of(uint8_t v, int k) { return v > k ? 0 : v; }       // an object that appears later: background
+__device__ __forceinline__ unsigned bit_of(int l) { return l ? 1u << (l - 1) : 0u; }
+
+struct LabelCounters {
+    int *lds;              // this wave's [k][6] table, used when the wave lies in one frame
+    int *counts;           // [k][T_all][6], at the first counted frame
+    int T_all;
+    bool one_frame;
+    __device__ __forceinline__ void add(int o, int t, int c) const {
+        if (one_frame) atomicAdd(&lds[o * 6 + c], 1);
+        else atomicAdd(&counts[((long)o * T_all + t) * 6 + c], 1);
+    }
+    __device__ __forceinline__ void add_set(unsigned set, int t, int c) const {
+        for (unsigned m = set; m; m &= m - 1) add(__ffs((int)m) - 1, t, c);
+    }
+};
+
+// every thread of the workgroup: the tables of its four waves -> global counters (a non-zero entry belongs to a wave inside one frame)
+__device__ __forceinline__ void flush_tables(const int (*tab)[LT], int k, long hw, int *__restrict__ counts, int T_all) {
+    for (int e = threadIdx.x; e < 4 * k * 6; e += 256) {
+        const int w = e / (k * 6), r = e - w * (k * 6);
+        const int v = tab[w][r];
+        if (!v) continue;
+        const int t = (int)((((long)blockIdx.x * 4 + w) * (64L * PPT)) / hw);
+        atomicAdd(&counts[((long)(r / 6) * T_all + t) * 6 + r % 6], v);
+    }
+}
+
+template <typename Wd>
+__global__ __launch_bounds__(256) void label_boundary_kernel(const uint8_t *__restrict__ gt, const uint8_t *__restrict__ pr, int k, int T, int H, int W,
+                                                             BSet<Wd> *__restrict__ bsets, int *__restrict__ counts, int T_all, int j_only) {
+    __shared__ int tab[4][LT];
+    for (int e = threadIdx.x; e < 4 * LT; e += 256) (&tab[0][0])[e] = 0;
+    __syncthreads();
+    const long hw = (long)H * W, n = T * hw;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long base = ((long)blockIdx.x * 4 + wv) * (64L * PPT);                          // first pixel of this wave
+    if (base < n) {
+        const long last = min(base + 64L * PPT, n) - 1;
+        const int t0 = (int)(base / hw);
+        const LabelCounters cn{tab[wv], counts, T_all, (int)(last / hw) == t0};
+        for (int j = 0; j < PPT; ++j) {
+            const long i = base + j * 64L + lane;
+            if (i >= n) break;
+            const int t = cn.one_frame ? t0 : (int)(i / hw);
+            const int g = label_of(gt[i], k), p = label_of(pr[i], k);
+            if (!j_only) {
+                const int rem = (int)(i - t * hw);
+                const int y = rem / W, x = rem - y * W;
+                auto bnd = [&](const uint8_t *seg, int s) -> unsigned {                      // _seg2bmap for every object at once
+                    const uint8_t *q = seg + i;
+                    unsigned b = 0;
+                    auto differ = [&](uint8_t v) { const int nb = label_of(v, k); if (nb != s) b |= bit_of(s) | bit_of(nb); };
+                    if (y < H - 1 && x < W - 1) { differ(q[1]); differ(q[W]); differ(q[W + 1]); }
+                    else if (y == H - 1 && x < W - 1) differ(q[1]);
+                    else if (x == W - 1 && y < H - 1) differ(q[W]);
+                    return b;
+                };
+                const unsigned bg = bnd(gt, g), bp = bnd(pr, p);
+                bsets[i] = BSet<Wd>{(Wd)bg, (Wd)bp};
+                cn.add_set(bg, t, 2);
+                cn.add_set(bp, t, 3);
+            }
+            if (g) { if (g == p) cn.add(g - 1, t, 0); cn.add(g - 1, t, 1); }                // union of o: every pixel that is o in either map
+            if (p && p != g) cn.add(p - 1, t, 1);
+        }
+    }
+    __syncthreads();
+    flush_tables(tab, k, hw, counts, T_all);
+}
+
+template <typename Wd>
+__global__ __launch_bounds__(256) void label_match_kernel(const BSet<Wd> *__restrict__ bsets, int k, int T, int H, int W, int r,
+                                                          int *__restrict__ counts, int T_all) {
+    __shared__ int tab[4][LT];
+    for (int e = threadIdx.x; e < 4 * LT; e += 256) (&tab[0][0])[e] = 0;
+    __syncthreads();
+    const long hw = (long)H * W, n = T * hw;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long base = ((long)blockIdx.x * 4 + wv) * (64L * PPT);
+    if (base < n) {
+        const long last = min(base + 64L * PPT, n) - 1;
+        const int t0 = (int)(base / hw);
+        const LabelCounters cn{tab[wv], counts, T_all, (int)(last / hw) == t0};
+        for (int j = 0; j < PPT; ++j) {
+            const long i = base + j * 64L + lane;
+            if (i >= n) break;
+            const BSet<Wd> me = bsets[i];
+            if (!(me.g | me.p)) continue;                     // only boundary pixels scan the disk
+            const int t = cn.one_frame ? t0 : (int)(i / hw);
+            const int rem = (int)(i - t * hw);
+            const int y = rem / W, x = rem - y * W;
+            const BSet<Wd> *b = bsets + (long)t * hw;
+            unsigned og = 0, op = 0;                          // objects whose gt / pred boundary lies inside the disk
+            for (int d = 0; d <= 2 * r && ((op & me.g) != me.g || (og & me.p) != me.p); ++d) {       // rows from the centre outwards
+                const int dy = (d & 1) ? -((d + 1) >> 1) : (d >> 1);
+                const int yy = y + dy;
+                if ((unsigned)yy >= (unsigned)H) continue;
+                int hx = 0;
+                while ((hx + 1) * (hx + 1) + dy * dy <= r * r) ++hx;
+                const int x0 = max(x - hx, 0), x1 = min(x + hx, W - 1);
+                const BSet<Wd> *row = b + (long)yy * W;
+                for (int xx = x0; xx <= x1; ++xx) { const BSet<Wd> v = row[xx]; og |= v.g; op |= v.p; }
+            }
+            cn.add_set(me.g & op, t, 4);                      // object o's gt boundary pixel inside ITS dilated pred boundary
+            cn.add_set(me.p & og, t, 5);
+        }
+    }
+    __syncthreads();
+    flush_tables(tab, k, hw, counts, T_all);
+}
+
+__global__ __launch_bounds__(256) void label_compose_kernel(const uint8_t *__restrict__ masks, int nh, int nw, int lh, int lw,
+                                                            const uint8_t *__restrict__ gt, const uint8_t *__restrict__ annotated, int k, int T, int H,
+                                                            int W, uint8_t *__restrict__ gen) {
+    const long hw = (long)H * W, n = T * hw;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int t = (int)(i / hw);
+        const int rem = (int)(i - t * hw);
+        const int y = rem / W, x = rem - y * W;
+        gen[i] = (uint8_t)label_of(annotated[t] ? gt[i] : masks[((long)t * nh + y + lh) * nw + x + lw], k);
+    }
+}
+
+// object_quality[o][t] as round_quality_kernel computes it from the counts of object o (NO_OBJECT where present[o][t] is 0), quality[t] = the
+// mean over the objects present in frame t - added in ascending o, correctly rounded, then one division by their number - or NO_OBJECT when
+// there is none; select = first index of the minimum of quality.  The host restatement is metrics.label_round_quality.
+__global__ __launch_bounds__(256) void label_quality_kernel(const int *__restrict__ counts, const uint8_t *__restrict__ present, int k, int T, int j_only,
+                                                            double no_object, double *__restrict__ object_quality, double *__restrict__ quality,
+                                                            int *__restrict__ select) {
+    double best = __builtin_inf();
+    int besti = 0x7fffffff;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        double sum = 0.0;
+        int cnt = 0;
+        for (int o = 0; o < k; ++o) {
+            double q = no_object;
+            if (present[o * T + t]) {
+                q = quality_of(counts + ((long)o * T + t) * 6, j_only);
+                sum = __dadd_rn(sum, q);
+                ++cnt;
+            }
+            object_quality[o * T + t] = q;
+        }
+        const double q = cnt ? __ddiv_rn(sum, (double)cnt) : no_object;
+        quality[t] = q;
+        if (q < best) { best = q; besti = t; }
+    }
+    block_argmin(best, besti, select);
+}
+
+size_t label_scratch_bytes(int k, int T, int H, int W) { return (size_t)T * H * W * (k <= 8 ? sizeof(BSet<uint8_t>) : sizeof(BSet<uint32_t>)); }
+
+template <typename Wd>
+static void label_counts_kernels(const uint8_t *gt, const uint8_t *pred, int k, int Tn, int H, int W, int radius, void *bsets, int *counts, int T_all,
+                                 unsigned blocks, hipStream_t s) {
+    hipLaunchKernelGGL(label_boundary_kernel<Wd>, dim3(blocks), dim3(256), 0, s, gt, pred, k, Tn, H, W, (BSet<Wd> *)bsets, counts, T_all, radius < 0 ? 1 : 0);
+    if (radius >= 0) hipLaunchKernelGGL(label_match_kernel<Wd>, dim3(blocks), dim3(256), 0, s, (const BSet<Wd> *)bsets, k, Tn, H, W, radius, counts, T_all);
+}
+
+void label_counts_launch(const uint8_t *gt, const uint8_t *pred, int k, int Tn, int H, int W, int radius, void *bsets, int *counts, int T_all,
+                         hipStream_t s) {
+    const long n = (long)Tn * H * W;
+    const unsigned blocks = (unsigned)((n + 256L * PPT - 1) / (256L * PPT));
+    // the Tn counted frames of every object: k rows of Tn * 6 ints, T_all * 6 ints apart
+    (void)hipMemset2DAsync(counts, (size_t)T_all * 6 * sizeof(int), 0, (size_t)Tn * 6 * sizeof(int), (size_t)k, s);
+    if (k <= 8) label_counts_kernels<uint8_t>(gt, pred, k, Tn, H, W, radius, bsets, counts, T_all, blocks, s);
+    else label_counts_kernels<uint32_t>(gt, pred, k, Tn, H, W, radius, bsets, counts, T_all, blocks, s);
+}
+
+void label_round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated,
+                              const uint8_t *present, int k, int Tn, int H, int W, int radius, double no_object, uint8_t *gen, void *bsets,
+                              int *counts, int T_all, double *object_quality, double *quality, int *select, hipStream_t s, int t0) {
+    const long n = (long)Tn * H * W;
+    const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(label_compose_kernel, dim3(blocks), dim3(256), 0, s, masks, nh, nw, lh, lw, gt, annotated, k, Tn, H, W, gen);
+    label_counts_launch(gt, gen, k, Tn, H, W, radius, bsets, counts, T_all, s);
+    hipLaunchKernelGGL(label_quality_kernel, dim3(1), dim3(256), 0, s, counts - (long)t0 * 6, present, k, T_all, radius < 0 ? 1 : 0, no_object,
+                       object_quality, quality, select);
 }
 
 }  // namespace stcn

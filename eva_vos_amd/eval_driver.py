@@ -13,7 +13,10 @@ Differences by design:
 * QNet frame selection keeps features on the device (``eva_vos_amd.qnet``);
 * two samples are in flight per GPU (host thread + HIP stream each, ``--lanes``): +9..17 % rounds/s;
 * samples are LPT-sharded over ranks instead of ``--min-idx/--max-idx``; ONE gather of fixed-width rows at the end
-  (RCCL over xGMI), rank 0 writes the CSV with the reference's columns ``video, mu_metric, annotation_time, round``.
+  (RCCL over xGMI), rank 0 writes the CSV with the reference's columns ``video, mu_metric, annotation_time, round``;
+* ``--multi-object`` (an additional mode; the reference's per-object protocol stays the default): ONE session per video with all its
+  objects in one engine - the key encoder runs once per frame, not once per frame and object - scored per round by the k-object
+  evaluation on the device (``stcn_metrics_objects_round``); rows stay one per (video, object, round) with the per-object sample ids.
 
 Usage:  python -m eva_vos_amd.eval_driver --root data/MOSE --imset data/MOSE/ImageSets/test.txt --policy oracle_mask
         (multi-GPU: python -m torch.distributed.run --nproc-per-node N -m eva_vos_amd.eval_driver ...)
@@ -35,6 +38,8 @@ from . import metrics, shard
 from .fq_driver import NO_OBJECT, ClipDataset, lane_engine_options, run_lanes
 
 POLICIES = ("oracle_mask", "rand_mask", "qnet_mask", "upper_bound_mask")
+MULTI_OBJECT_POLICIES = ("oracle_mask", "rand_mask")          # QNet takes one binary mask; the upper bound builds on the one-object scorer
+MAX_OBJECTS = 32                                              # STCN_MAX_OBJECTS
 MASK_SECONDS, SKIP_SECONDS = 80, 3            # annotation cost model of interactions/mask.py:33-36
 
 
@@ -77,11 +82,48 @@ def _upper_bound_frame(processor, gt, gt_thw, frames, metric):
     return best_f
 
 
-def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and_f", qnet=None, rng=None):
+def _run_policy_multi_object(policy: str, processor, sample, rounds: int, metric: str, rng):
+    """One VIDEO with all its k objects through ``rounds`` annotation rounds in one engine (``InferenceCore(..., num_objects=k)``): the
+    annotation of frame f is the (k+1)-channel one-hot of its label map, background first, through the reference's ``scribble=True`` path;
+    a round is scored by the k-object evaluation on the device.  The oracle policy takes the arg-min of the FRAME quality (the mean over
+    the objects present in the frame); a frame is valid while any object is present in it."""
+    T, k = sample["num_frames"], int(sample["num_objects"])
+    dev = processor.prob.device
+    scorer = metrics.RoundScorer(sample["gt"][0, :, 0].to(dev), "j" if metric == "j" else "j_and_f", max_rounds=max(rounds, 1),
+                                 no_object=NO_OBJECT, num_objects=k)
+    empty = scorer.empty_host
+    valid = set(np.where(~empty)[0].tolist())
+    channels = torch.arange(k + 1, device=dev, dtype=torch.uint8)[:, None, None, None]
+    frames, times, scored, propagated = [0], [MASK_SECONDS], 0, 0
+    for r in range(1, rounds + 1):
+        if r >= T or (scored and not (valid - set(frames))):       # not_avail_frames, with "frame without any object"
+            continue
+        f = frames[r - 1]
+        processor.interact((scorer.gt[f][None, None] == channels).float(), f, scribble=True, download=False)      # [k+1,1,H,W]
+        propagated += processor.stats()["frames"]
+        worst, _ = scorer.score(processor, frames, keep_gen=False)
+        scored += 1
+        sel = worst if policy == "oracle_mask" else rng.choice(sorted(set(range(T)) - set(frames)))
+        times.append(SKIP_SECONDS if empty[sel] else MASK_SECONDS)
+        frames.append(sel)
+    q, oq = scorer.qualities(), scorer.object_qualities()
+    per_round = [q[i].copy() for i in range(scored)]
+    mus = [float(np.mean(row[~empty])) if (~empty).any() else float("nan") for row in per_round]
+    return dict(mu_metrics=mus, annotation_times=times[:-1], frames=frames, round_metrics=per_round, propagated_frames=propagated,
+                object_metrics=[oq[i].copy() for i in range(scored)], present=scorer.present_host)
+
+
+def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and_f", qnet=None, rng=None, multi_object: bool = False):
     """One sample through ``rounds`` annotation rounds.  Returns dict(mu_metrics, annotation_times, frames,
     round_metrics): mu_metrics[r] / annotation_times[r] as the reference returns them; frames = annotated frames in
-    order; round_metrics[r] = per-frame quality after round r."""
+    order; round_metrics[r] = per-frame quality after round r.
+    ``multi_object``: the sample is a per-video one (``ClipDataset(..., per_video=True)``), the processor holds all its objects; the
+    values above are those of the FRAME quality, and ``object_metrics[r]`` [k,T] / ``present`` [k,T] are added."""
     assert policy in POLICIES, policy
+    if multi_object:
+        if policy not in MULTI_OBJECT_POLICIES:
+            raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
+        return _run_policy_multi_object(policy, processor, sample, rounds, metric, rng or random)
     T = sample["num_frames"]
     dev = processor.prob.device
     gt = sample["gt"][0].to(dev)                                   # [T,1,H,W]
@@ -121,33 +163,53 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
 
 
 def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "oracle_mask", rounds: int = 60,
-        metric: str = "j_and_f", qnet=None, seed: int = 0, device: str = "cuda", lanes: int = 2, stats: dict = None):
+        metric: str = "j_and_f", qnet=None, seed: int = 0, device: str = "cuda", lanes: int = 2, stats: dict = None,
+        multi_object: bool = False):
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
     (rows: sample id, round, mu_metric, annotation_time, annotated frame, T, then T per-frame values, NaN-padded).
-    `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited) and `interactions` are added to it."""
+    `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited) and `interactions` are added to it.
+    `multi_object`: one session per VIDEO with all its objects in one engine.  The rows keep their schema and the sample ids of the per-object
+    enumeration, one per (video, object, round), so the outputs of the two modes join on (sample id, round): mu_metric = the mean of that
+    object's quality over the frames where it is present, annotation_time = 80 s if the object is present in the annotated frame, else
+    3 s, the annotated frame is the session's, the per-frame values are that object's."""
     import torch.distributed as dist
 
     from mivos.inference_core import InferenceCore
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
-    ds = ClipDataset(root, imset)
+    if multi_object and policy not in MULTI_OBJECT_POLICIES:
+        raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
+    ds = ClipDataset(root, imset, per_video=multi_object)
+    for v, k, _ in ds.samples if multi_object else ():
+        if k > MAX_OBJECTS:
+            raise ValueError(f"video {v} has {k} objects: a multi-object session holds at most {MAX_OBJECTS}")
     t_max = max(s[2] for s in ds.samples)
-    mine = sorted(shard.lpt_assign([s[2] for s in ds.samples], world)[rank])
+    mine = sorted(shard.lpt_assign([s[2] * (s[1] if multi_object else 1) for s in ds.samples], world)[rank])      # multi-object: frames x objects
     width = 6 + t_max
     stats_lock = __import__("threading").Lock()
 
     def work(i, sample):
         rows = []
         t_c = time.perf_counter()
-        proc = InferenceCore(prop_net, fuse_net, sample["rgb"], 1, engine_options=lane_engine_options(lanes))
+        proc = InferenceCore(prop_net, fuse_net, sample["rgb"], sample["num_objects"] if multi_object else 1, engine_options=lane_engine_options(lanes))
         t_s = time.perf_counter()
-        res = run_policy(policy, proc, sample, rounds, metric, qnet, random.Random(seed * 100003 + i))
+        res = run_policy(policy, proc, sample, rounds, metric, qnet, random.Random(seed * 100003 + i), multi_object=multi_object)
         if stats is not None:
             with stats_lock:
                 stats["create_s"] = stats.get("create_s", 0.0) + t_s - t_c
                 stats["session_s"] = stats.get("session_s", 0.0) + time.perf_counter() - t_s
                 stats["propagated_frames"] = stats.get("propagated_frames", 0) + res["propagated_frames"]
                 stats["interactions"] = stats.get("interactions", 0) + len(res["mu_metrics"])
+        if multi_object:
+            for o, sid in enumerate(sample["object_ids"]):
+                here = res["present"][o]
+                for r, oq in enumerate(res["object_metrics"]):
+                    row = np.full(width, np.nan, np.float32)
+                    f = res["frames"][r]
+                    row[:6] = (sid, r, float(np.mean(oq[o][here])) if here.any() else float("nan"), MASK_SECONDS if here[f] else SKIP_SECONDS, f, oq.shape[1])
+                    row[6:6 + oq.shape[1]] = oq[o]
+                    rows.append(row)
+            return rows
         for r, (mu, sec, q) in enumerate(zip(res["mu_metrics"], res["annotation_times"], res["round_metrics"])):
             row = np.full(width, np.nan, np.float32)
             row[:6] = (i, r, mu, sec, res["frames"][r], len(q))
@@ -155,7 +217,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
             rows.append(row)
         return rows
 
-    rows = run_lanes(root, imset, mine, lanes, work, device, stats)
+    rows = run_lanes(root, imset, mine, lanes, work, device, stats, per_video=multi_object)
     allrows = shard.gather_rows(np.stack(rows) if rows else np.zeros((0, width), np.float32), width)
     if rank == 0 and out_csv:
         os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
@@ -164,7 +226,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
             wr = csv.writer(f)
             wr.writerow(["video", "mu_metric", "annotation_time", "round"])
             for row in allrows[order]:
-                wr.writerow([ds.name(int(row[0])), float(row[2]), int(row[3]), int(row[1])])
+                wr.writerow([ds.object_names[int(row[0])], float(row[2]), int(row[3]), int(row[1])])
     return allrows
 
 
@@ -175,6 +237,8 @@ def main():
     ap.add_argument("--policy", default="oracle_mask", choices=POLICIES)
     ap.add_argument("--rounds", type=int, default=60)
     ap.add_argument("--lanes", type=int, default=2, help="videos in flight per GPU")
+    ap.add_argument("--multi-object", action="store_true", help="one session per video with all its objects in one engine (policies: "
+                    + ", ".join(MULTI_OBJECT_POLICIES) + "); default: one session per (video, object), the reference's protocol")
     ap.add_argument("--db", default="MOSE")
     ap.add_argument("--prop-weights", default="./model_weights/mivos/stcn.pth")
     ap.add_argument("--fusion-weights", default="./model_weights/mivos/fusion.pth")
@@ -207,7 +271,7 @@ def main():
     if qnet is not None:
         qnet = qnet.cuda().eval()
     out = os.path.join("Experiments", a.db, f"{a.policy}.csv")
-    rows = run(a.root, a.imset, out, prop.eval(), fuse.eval(), a.policy, a.rounds, qnet=qnet, lanes=a.lanes)
+    rows = run(a.root, a.imset, out, prop.eval(), fuse.eval(), a.policy, a.rounds, qnet=qnet, lanes=a.lanes, multi_object=a.multi_object)
     if not dist.is_initialized() or dist.get_rank() == 0:
         print(f"{len(rows)} rounds -> {out}")
     if dist.is_initialized():

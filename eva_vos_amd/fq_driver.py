@@ -132,20 +132,33 @@ def decode_pool():
 
 class ClipDataset:
     """DAVIS/MOSE directory layout: JPEGImages/480p/<video>/%05d.jpg, Annotations/480p/<video>/%05d.png
-    (palette index = object id).  One sample per (video, object), named ``<video>__<obj>``."""
+    (palette index = object id).  One sample per (video, object), named ``<video>__<obj>``.
 
-    def __init__(self, root: str, imset: str, resolution: str = "480p"):
+    ``per_video=True`` is the view of the multi-object sessions: one sample per video that has an object, named ``<video>``, with the
+    label map itself as ``gt`` (uint8 [1,T,1,H,W]), ``num_objects`` = k (the largest label of the first frame, as the per-object view
+    counts them) and ``object_ids`` = the k sample ids the per-object view gives its objects.  Same decoded clip cache."""
+
+    def __init__(self, root: str, imset: str, resolution: str = "480p", per_video: bool = False):
         self.image_dir = os.path.join(root, "JPEGImages", resolution)
         self.mask_dir = os.path.join(root, "Annotations", resolution)
-        self.samples: List[tuple] = []          # (video, object id, frames)
+        self.per_video = per_video
+        self.samples: List[tuple] = []          # (video, object id, frames); per_video: (video, number of objects, frames)
+        self.object_names: List[str] = []       # per-object sample id -> <video>__<obj>, in either view
+        self.first_object_id: List[int] = []    # per_video: the per-object sample id of object 1 of sample i
         for line in open(imset):
             v = line.strip()
             if not v:
                 continue
             first = np.array(Image.open(os.path.join(self.mask_dir, v, "00000.png")).convert("P"))
             n = len(os.listdir(os.path.join(self.image_dir, v)))
-            for obj in range(1, int(first.max()) + 1):
-                self.samples.append((v, obj, n))
+            k = int(first.max())
+            if per_video and k > 0:
+                self.samples.append((v, k, n))
+                self.first_object_id.append(len(self.object_names))
+            for obj in range(1, k + 1):
+                if not per_video:
+                    self.samples.append((v, obj, n))
+                self.object_names.append(f"{v}__{obj}")
         self._cache: Dict[str, tuple] = {}
 
     def __len__(self):
@@ -153,7 +166,7 @@ class ClipDataset:
 
     def name(self, i):
         v, o, _ = self.samples[i]
-        return f"{v}__{o}"
+        return v if self.per_video else f"{v}__{o}"
 
     def _clip(self, video: str, n: int):
         """Decoded once per video (samples of a video are adjacent): the frames as uint8 [T,H,W,3] - pinned when a GPU is there, so
@@ -211,6 +224,10 @@ class ClipDataset:
     def _meta(self, i):
         v, obj, n = self.samples[i]
         entry = self._clip(v, n)
+        if self.per_video:                                         # obj is the number of objects here
+            first = self.first_object_id[i]
+            return entry, {"gt": entry[1][None, :, None], "name": v, "video": v, "num_frames": n, "num_objects": obj,
+                           "object_ids": list(range(first, first + obj))}
         gt = (entry[1] == obj).float()[None, :, None]              # [1,T,1,H,W], no bg channel (reference layout)
         return entry, {"gt": gt, "name": self.name(i), "video": v, "num_frames": n}
 
@@ -275,11 +292,11 @@ def lane_engine_options(lanes: int):
     return {"lookahead": 0} if lanes > 1 and "STCN_LOOKAHEAD" not in os.environ else None
 
 
-def run_lanes(root: str, imset: str, mine, lanes: int, work, device: str = "cuda", stats: dict = None):
+def run_lanes(root: str, imset: str, mine, lanes: int, work, device: str = "cuda", stats: dict = None, per_video: bool = False):
     """Process the samples `mine` on `lanes` host threads, each with its own HIP stream, clip loader and prefetcher
     (samples are independent; two videos in flight fill each other's kernel tails, as bench.py's lanes do).
     work(i, sample) -> list of rows; returns all rows.  Chunks are contiguous so that the objects of one video stay
-    with one loader (per-video decode cache)."""
+    with one loader (per-video decode cache).  ``per_video``: the indices are those of ``ClipDataset(..., per_video=True)``."""
     from concurrent.futures import ThreadPoolExecutor
     mine = list(mine)
     lanes = max(1, min(lanes, len(mine)))
@@ -288,7 +305,7 @@ def run_lanes(root: str, imset: str, mine, lanes: int, work, device: str = "cuda
     bounds = [len(mine) * l // lanes for l in range(lanes + 1)]
 
     def lane(l):
-        ds = ClipDataset(root, imset)
+        ds = ClipDataset(root, imset, per_video=per_video)
         rows = []
         if on_gpu:
             torch.cuda.set_device(dev_index)

@@ -81,6 +81,50 @@ def _scores_from_counts(c: np.ndarray) -> np.ndarray:
     return out
 
 
+def label_counts(gt: np.ndarray, gen: np.ndarray, num_objects: int) -> np.ndarray:
+    """Label maps [T,H,W] (0 = background, o in 1..k = object o, a label above k = background) -> int64 [k,T,6]: per object and frame
+    the six integers of ``stcn_metrics_jf_counts`` on the binary masks ``gt == o`` and ``gen == o`` (host: NumPy / SciPy)."""
+    gt, gen = np.asarray(gt), np.asarray(gen)
+    T, H, W = gt.shape
+    se = _disk(int(np.ceil(0.008 * np.linalg.norm((H, W)))))
+    c = np.zeros((num_objects, T, 6), np.int64)
+    for o in range(1, num_objects + 1):
+        for t in range(T):
+            g, p = gt[t] == o, gen[t] == o
+            gb, fb = boundary_map(g), boundary_map(p)
+            c[o - 1, t] = ((g & p).sum(), (g | p).sum(), gb.sum(), fb.sum(),
+                           (gb & ndimage.binary_dilation(fb, se)).sum() if fb.any() else 0,
+                           (fb & ndimage.binary_dilation(gb, se)).sum() if gb.any() else 0)
+    return c
+
+
+def label_round_quality(gt: np.ndarray, gen: np.ndarray, num_objects: int, metric: str = "j_and_f", no_object: float = 20.0, counts=None):
+    """The evaluation of one round of a k-object session, restated on the host - the yardstick of ``stcn_metrics_objects_round``.
+    gt, gen: label maps [T,H,W] (gen = the evaluated map: ground truth on annotated frames, the engine's labels elsewhere).
+    Returns (q [k,T], Q [T], selection), float64:
+    q[o][t] = J (``metric == "j"``) or J&F of object o + 1 in frame t from its counts as ``_scores_from_counts`` computes them, ``no_object``
+    where ``gt == o + 1`` is empty in frame t;  Q[t] = the mean of q[.][t] over the objects present in the ground truth of frame t - added
+    in ascending o, then divided by their number - or ``no_object`` when there is none;  selection = ``numpy.argmin(Q)``.
+    ``counts`` (optional [k,T,6]): use these instead of counting on the host."""
+    gt = np.asarray(gt)
+    k, T = int(num_objects), gt.shape[0]
+    c = label_counts(gt, gen, k) if counts is None else np.asarray(counts)
+    col = 0 if metric == "j" else 2
+    q = np.full((k, T), float(no_object), np.float64)
+    Q = np.full(T, float(no_object), np.float64)
+    present = np.stack([(gt == o).reshape(T, -1).any(1) for o in range(1, k + 1)])
+    for o in range(k):
+        q[o, present[o]] = _scores_from_counts(c[o])[present[o], col]
+    for t in range(T):
+        s, n = 0.0, 0
+        for o in range(k):
+            if present[o, t]:
+                s, n = s + float(q[o, t]), n + 1
+        if n:
+            Q[t] = s / n
+    return q, Q, int(np.argmin(Q))
+
+
 def sequence_scores_gpu(gt, pred, j_only: bool = False):
     """J, F, J&F per frame on the GPU (HIP kernels behind ``stcn_metrics_jf_counts``).
     gt, pred: torch uint8/bool tensors [T,H,W] on the same cuda device (non-zero = object).
@@ -113,6 +157,57 @@ def sequence_scores_gpu(gt, pred, j_only: bool = False):
     return _scores_from_counts(c)
 
 
+def _check_num_objects(k) -> int:
+    k = int(k)
+    if not 1 <= k <= 32:
+        raise ValueError(f"num_objects = {k}: the library is built for 1..32 objects (STCN_MAX_OBJECTS)")
+    return k
+
+
+def _objects_scratch(k: int, T: int, H: int, W: int, device):
+    """The boundary scratch of the k-object metric calls, sized by the library (``stcn_metrics_objects_scratch``) and by nothing else."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    n = C.c_int64()
+    _lib.check(_lib.lib().stcn_metrics_objects_scratch(k, T, H, W, C.byref(n)), "stcn_metrics_objects_scratch")
+    return torch.empty((int(n.value),), dtype=torch.uint8, device=device)
+
+
+def sequence_scores_objects_gpu(gt, pred, num_objects: int, j_only: bool = False):
+    """``sequence_scores_gpu`` for label maps of ``num_objects`` objects: gt, pred uint8 [T,H,W] on the same cuda device (0 = background,
+    o = object o, a label above ``num_objects`` = background).  Returns float64 [k,T,3] - rows (J, F, J&F) of object o + 1 as
+    ``sequence_scores_gpu(gt == o + 1, pred == o + 1)`` returns them - from ONE pass over the pixels (``stcn_metrics_objects_jf_counts``;
+    ``j_only``: ``stcn_metrics_objects_j_counts``, columns 1 and 2 NaN)."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    k = _check_num_objects(num_objects)
+    assert gt.is_cuda and pred.is_cuda and gt.shape == pred.shape and gt.dim() == 3 and gt.dtype == pred.dtype == torch.uint8
+    gt, pred = gt.contiguous(), pred.contiguous()
+    T, H, W = gt.shape
+    with torch.cuda.device(gt.device):
+        counts = torch.empty((k, T, 6), dtype=torch.int32, device=gt.device)
+        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if j_only:
+            _lib.check(_lib.lib().stcn_metrics_objects_j_counts(s, C.c_void_p(gt.data_ptr()), C.c_void_p(pred.data_ptr()), k, T, H, W,
+                                                                C.c_void_p(counts.data_ptr())), "stcn_metrics_objects_j_counts")
+            c = counts.cpu().numpy()
+            out = np.full((k, T, 3), np.nan)
+            out[..., 0] = np.where(c[..., 1] > 0, c[..., 0] / np.maximum(c[..., 1], 1), 0.0)
+            return out
+        scratch = _objects_scratch(k, T, H, W, gt.device)
+        _lib.check(_lib.lib().stcn_metrics_objects_jf_counts(s, C.c_void_p(gt.data_ptr()), C.c_void_p(pred.data_ptr()), k, T, H, W,
+                                                             C.c_void_p(counts.data_ptr()), C.c_void_p(scratch.data_ptr())),
+                   "stcn_metrics_objects_jf_counts")
+        c = counts.cpu().numpy()
+    return np.stack([_scores_from_counts(c[o]) for o in range(k)])
+
+
 class RoundScorer:
     """The per-round evaluation of an annotation session, kept on the device (``stcn_metrics_round``): after every ``interact()`` the
     reference's loops compute per-frame J or J&F of the propagated masks against the ground truth (annotated frames counting with their
@@ -120,22 +215,45 @@ class RoundScorer:
     (interactions/mask.py:130-133).  Here one C call enqueues compose + counts + fp64 quality + arg-min on the engine's stream; only the
     selected frame (4 bytes) crosses PCIe per round - the host waits for it on a BLOCKING event (it sleeps instead of spinning a core) -
     and the quality rows of all rounds are fetched together at the end of the session (``qualities()``).  Bit-identical to the host path
-    (``sequence_scores_gpu`` + NumPy), which the tests assert."""
+    (``sequence_scores_gpu`` + NumPy), which the tests assert.
 
-    def __init__(self, gt_thw, metric: str = "j", max_rounds: int = 64, no_object: float = 20.0):
+    ``num_objects=k`` scores a MULTI-OBJECT session (``stcn_metrics_objects_round``): ``gt_thw`` is a uint8 label map (0 = background,
+    o in 1..k = object o, a label above k = background), ``processor`` an engine built with ``num_objects=k``, ``gen`` the evaluated label map.
+    The frame quality is the mean of the per-object qualities over the objects present in the frame's ground truth (``label_round_quality``
+    is the host restatement, bit-identical); ``object_qualities()`` returns the per-object rows.  Still one enqueue sequence - its length does
+    not depend on k - and one 4-byte download per round."""
+
+    def __init__(self, gt_thw, metric: str = "j", max_rounds: int = 64, no_object: float = 20.0, num_objects=None):
         import torch
         assert gt_thw.is_cuda and gt_thw.dim() == 3
         self.metric, self.no_object = metric, float(no_object)
         self.dev = gt_thw.device
-        self.gt = (gt_thw > 0.5 if gt_thw.is_floating_point() else gt_thw != 0).to(torch.uint8).contiguous()
+        self.k = None if num_objects is None else _check_num_objects(num_objects)
+        if self.k is None:
+            self.gt = (gt_thw > 0.5 if gt_thw.is_floating_point() else gt_thw != 0).to(torch.uint8).contiguous()
+        else:
+            assert gt_thw.dtype == torch.uint8, "a label map is uint8"
+            self.gt = torch.where(gt_thw > self.k, torch.zeros_like(gt_thw), gt_thw).contiguous()      # objects that appear later: background
         self.T, self.H, self.W = (int(v) for v in self.gt.shape)
-        empty = self.gt.flatten(1).sum(1) == 0
+        if self.k is not None:
+            present = torch.stack([(self.gt == o).flatten(1).any(1) for o in range(1, self.k + 1)])     # [k,T], once per sample
+            self.present = present.to(torch.uint8).contiguous()
+            self.present_host = present.cpu().numpy()                 # ONE sync per sample
+            empty = ~present.any(0)                                   # frames without any object carry the NO_OBJECT token
+            self.object_quality = torch.empty((max_rounds, self.k, self.T), dtype=torch.float64, device=self.dev)
+        else:
+            empty = self.gt.flatten(1).sum(1) == 0
         self.noobj = empty.to(torch.uint8).contiguous()
         self.empty_host = empty.cpu().numpy()                         # ONE sync per sample: which frames carry the NO_OBJECT token
         self.annotated = torch.zeros(self.T, dtype=torch.uint8, device=self.dev)
         self.flags_host = torch.zeros(self.T, dtype=torch.uint8).pin_memory()
-        self.counts = torch.empty((self.T, 6), dtype=torch.int32, device=self.dev)
-        self.scratch = None if metric == "j" else torch.empty((self.T * self.H * self.W,), dtype=torch.uint8, device=self.dev)
+        self.counts = torch.empty((self.T, 6) if self.k is None else (self.k, self.T, 6), dtype=torch.int32, device=self.dev)
+        if metric == "j":
+            self.scratch = None
+        elif self.k is None:
+            self.scratch = torch.empty((self.T * self.H * self.W,), dtype=torch.uint8, device=self.dev)
+        else:
+            self.scratch = _objects_scratch(self.k, self.T, self.H, self.W, self.dev)
         self.quality = torch.empty((max_rounds, self.T), dtype=torch.float64, device=self.dev)
         self.select = torch.empty((max_rounds,), dtype=torch.int32, device=self.dev)
         self.select_host = torch.empty((max_rounds,), dtype=torch.int32).pin_memory()
@@ -177,10 +295,17 @@ class RoundScorer:
                 gen = prev
             self._gen = gen
             p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-            _lib.check(_lib.lib().stcn_metrics_round(
-                C.c_void_p(torch.cuda.current_stream().cuda_stream), p(processor.masks), processor.nh, processor.nw, lh, lw, p(self.gt),
-                p(self.annotated), p(self.noobj), self.T, self.H, self.W, t0, t1, 1 if self.metric == "j" else 0, self.no_object, p(gen),
-                p(self.scratch), p(self.counts), p(self.quality[r]), p(self.select[r:r + 1])), "stcn_metrics_round")
+            if self.k is None:
+                _lib.check(_lib.lib().stcn_metrics_round(
+                    C.c_void_p(torch.cuda.current_stream().cuda_stream), p(processor.masks), processor.nh, processor.nw, lh, lw, p(self.gt),
+                    p(self.annotated), p(self.noobj), self.T, self.H, self.W, t0, t1, 1 if self.metric == "j" else 0, self.no_object, p(gen),
+                    p(self.scratch), p(self.counts), p(self.quality[r]), p(self.select[r:r + 1])), "stcn_metrics_round")
+            else:
+                _lib.check(_lib.lib().stcn_metrics_objects_round(
+                    C.c_void_p(torch.cuda.current_stream().cuda_stream), p(processor.masks), processor.nh, processor.nw, lh, lw, p(self.gt),
+                    p(self.annotated), p(self.present), self.k, self.T, self.H, self.W, t0, t1, 1 if self.metric == "j" else 0, self.no_object,
+                    p(gen), p(self.scratch), p(self.counts), p(self.object_quality[r]), p(self.quality[r]), p(self.select[r:r + 1])),
+                    "stcn_metrics_objects_round")
             self.select_host[r:r + 1].copy_(self.select[r:r + 1], non_blocking=True)
             self.event.record()
             self.event.synchronize()                                  # blocking wait: the lane's host thread sleeps until the round is done
@@ -190,3 +315,9 @@ class RoundScorer:
     def qualities(self):
         """float64 [rounds, T]: the per-frame quality of every round scored so far (one D2H copy)."""
         return self.quality[: self.rounds].cpu().numpy()
+
+    def object_qualities(self):
+        """float64 [rounds, k, T]: the per-object quality of every round of a multi-object session scored so far (one D2H copy)."""
+        if self.k is None:
+            raise RuntimeError("RoundScorer.object_qualities: a one-object scorer (num_objects=None) has the rows of qualities() only")
+        return self.object_quality[: self.rounds].cpu().numpy()

@@ -416,6 +416,38 @@ int stcn_metrics_round(void *stream, const uint8_t *masks_dev, int nh, int nw, i
                        const uint8_t *noobj_dev, int T, int H, int W, int t0, int t1, int j_only, double no_object, uint8_t *gen_dev, uint8_t *scratch_dev,
                        int32_t *counts_dev, double *quality_dev, int32_t *select_dev);
 
+/* ---- the same for LABEL MAPS of k objects (multi-object annotation sessions) -------------------------------------------------
+ * A label map is uint8, 0 = background, o in 1..k = object o (the engine's mask tensor for num_objects = k; the palette-index ground truth);
+ * a label above k - an object that first appears later - counts as background for every object.  1 <= k <= STCN_MAX_OBJECTS.
+ * All objects are served by ONE pass over the pixels: the number of launches does not depend on k.
+ *
+ * Boundary scratch of the calls below for k objects and T frames of H x W, in BYTES (the one statement of its size: a per-pixel set of
+ * objects per map - bytes for k <= 8, 32-bit words above).  Works without a GPU. */
+int stcn_metrics_objects_scratch(int k, int T, int H, int W, int64_t *bytes);
+/* Per object the counts of stcn_metrics_jf_counts for the binary masks (gt == o), (pred == o), integer-exact:
+ *   gt_dev, pred_dev : uint8 [T,H,W] label maps;  counts_dev : int32 [k,T,6] OUT;  scratch_dev : stcn_metrics_objects_scratch bytes.
+ * Enqueues on `stream`, no sync. */
+int stcn_metrics_objects_jf_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int k, int T, int H, int W,
+                                   int32_t *counts_dev, void *scratch_dev);
+/* The region measure alone, as stcn_metrics_j_counts: columns 0 and 1 of counts_dev [k,T,6] filled, the others zero; no scratch. */
+int stcn_metrics_objects_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int k, int T, int H, int W, int32_t *counts_dev);
+/* One annotation round of a k-object session scored on the device (enqueue only), the counterpart of stcn_metrics_round:
+ *   masks_dev          : the engine's uint8 [T][nh][nw] label tensor, cropped at (lh, lw) to H x W
+ *   gt_dev             : uint8 [T,H,W] ground-truth label map;  annotated_dev : uint8 [T] flags
+ *   present_dev        : uint8 [k,T], non-zero where (gt == o) is not empty in frame t
+ *   gen_dev            : uint8 [T,H,W] OUT - the evaluated label map (engine labels, ground truth on annotated frames; labels above k as 0)
+ *   scratch_dev        : stcn_metrics_objects_scratch bytes (unused when j_only);  counts_dev : int32 [k,T,6] OUT
+ *   object_quality_dev : double [k,T] OUT - J (j_only) or J&F of object o in frame t as stcn_metrics_round computes it from the counts,
+ *                        no_object where the object is not present
+ *   quality_dev        : double [T] OUT - the mean of object_quality over the objects present in the frame: added in ascending o, then divided
+ *                        by their number (correctly rounded fp64, bit-identical to eva_vos_amd.metrics.label_round_quality); no_object for a
+ *                        frame without any object;  select_dev : int32 [1] OUT - first index of the minimum of quality_dev (numpy.argmin)
+ * [t0, t1) as in stcn_metrics_round: only those frames are composed and counted, quality / select cover all T frames. */
+int stcn_metrics_objects_round(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev,
+                               const uint8_t *annotated_dev, const uint8_t *present_dev, int k, int T, int H, int W, int t0, int t1, int j_only,
+                               double no_object, uint8_t *gen_dev, void *scratch_dev, int32_t *counts_dev, double *object_quality_dev,
+                               double *quality_dev, int32_t *select_dev);
+
 #ifdef __cplusplus
 }
 #endif
