@@ -423,22 +423,71 @@ int stcn_test_fusion(const stcn_model *m, void *stream, const float *img, const 
     return STCN_OK;
 }
 
+// ---- J / F metrics: every argument is checked before any device call --------------------------------------------------------------------
+static int bound_radius(int H, int W) { return (int)std::ceil(0.008 * std::sqrt((double)H * H + (double)W * W)); }      // interactions/metrics.py:119-120
+
+// What all seven entry points check: k where the call has one (label maps), the shape - min_hw = 2 where a boundary map can be built, 1 for
+// the binary J-only call - and every pointer the call dereferences.
+static bool metric_args_ok(const char *who, bool has_k, int k, int T, int H, int W, int min_hw, std::initializer_list<const void *> ptrs) {
+    if (has_k && (k < 1 || k > STCN_MAX_OBJECTS)) { set_error("%s: k = %d outside 1..%d (STCN_MAX_OBJECTS)", who, k, STCN_MAX_OBJECTS); return false; }
+    if (T < 1 || H < min_hw || W < min_hw) { set_error("%s: bad shape (T >= 1, H, W >= %d required; T=%d H=%d W=%d)", who, min_hw, T, H, W); return false; }
+    for (const void *p : ptrs)
+        if (!p) { set_error("%s: null pointer", who); return false; }
+    return true;
+}
+
 int stcn_metrics_jf_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int T, int H, int W,
                            int32_t *counts_dev, uint8_t *scratch_dev) {
-    if (!gt_dev || !pred_dev || !counts_dev || !scratch_dev || T < 1 || H < 2 || W < 2) {
-        set_error("stcn_metrics_jf_counts: bad arguments");
-        return STCN_E_INVALID;
-    }
-    // bound_pix = ceil(0.008 * ||(H, W)||)  (interactions/metrics.py:119-120)
-    const int radius = (int)std::ceil(0.008 * std::sqrt((double)H * H + (double)W * W));
-    jf_counts_launch(gt_dev, pred_dev, T, H, W, radius, scratch_dev, counts_dev, (hipStream_t)stream);
+    if (!metric_args_ok("stcn_metrics_jf_counts", false, 0, T, H, W, 2, {gt_dev, pred_dev, counts_dev, scratch_dev})) return STCN_E_INVALID;
+    jf_counts_launch(gt_dev, pred_dev, T, H, W, bound_radius(H, W), scratch_dev, counts_dev, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return STCN_OK;
 }
 
 int stcn_metrics_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int T, int H, int W, int32_t *counts_dev) {
-    if (!gt_dev || !pred_dev || !counts_dev || T < 1 || H < 1 || W < 1) { set_error("stcn_metrics_j_counts: bad arguments"); return STCN_E_INVALID; }
+    if (!metric_args_ok("stcn_metrics_j_counts", false, 0, T, H, W, 1, {gt_dev, pred_dev, counts_dev})) return STCN_E_INVALID;
     jf_counts_launch(gt_dev, pred_dev, T, H, W, -1, nullptr, counts_dev, (hipStream_t)stream);       // radius < 0: intersection / union only
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
+int stcn_metrics_objects_scratch(int k, int T, int H, int W, int64_t *bytes) {
+    if (!metric_args_ok("stcn_metrics_objects_scratch", true, k, T, H, W, 2, {bytes})) return STCN_E_INVALID;
+    *bytes = (int64_t)label_scratch_bytes(k, T, H, W);
+    return STCN_OK;
+}
+
+int stcn_metrics_objects_jf_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int k, int T, int H, int W, int32_t *counts_dev,
+                                   void *scratch_dev) {
+    if (!metric_args_ok("stcn_metrics_objects_jf_counts", true, k, T, H, W, 2, {gt_dev, pred_dev, counts_dev, scratch_dev})) return STCN_E_INVALID;
+    label_counts_launch(gt_dev, pred_dev, k, T, H, W, bound_radius(H, W), scratch_dev, counts_dev, T, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
+int stcn_metrics_objects_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int k, int T, int H, int W, int32_t *counts_dev) {
+    if (!metric_args_ok("stcn_metrics_objects_j_counts", true, k, T, H, W, 2, {gt_dev, pred_dev, counts_dev})) return STCN_E_INVALID;
+    label_counts_launch(gt_dev, pred_dev, k, T, H, W, -1, nullptr, counts_dev, T, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
+// Both round entry points.  labels: label maps of k objects, flags = present; else binary masks, flags = noobj, no object_quality.  Frames
+// [t0, t1) are composed and counted now; the counts (and gen) of the other frames are the caller's from earlier rounds.
+static int metrics_round(const char *who, bool labels, void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev,
+                         const uint8_t *annotated_dev, const uint8_t *flags_dev, int k, int T, int H, int W, int t0, int t1, int j_only, double no_object,
+                         uint8_t *gen_dev, void *scratch_dev, int32_t *counts_dev, double *object_quality_dev, double *quality_dev, int32_t *select_dev) {
+    const void *unused = who;       // in the place of a pointer that this form of the call does not read
+    if (!metric_args_ok(who, labels, k, T, H, W, 2, {masks_dev, gt_dev, annotated_dev, flags_dev, gen_dev, counts_dev, labels ? object_quality_dev : unused,
+                                                    quality_dev, select_dev, j_only ? unused : scratch_dev}))
+        return STCN_E_INVALID;
+    if (lh < 0 || lw < 0 || lh + H > nh || lw + W > nw) { set_error("%s: the %d x %d crop at (%d, %d) leaves the %d x %d tensor", who, H, W, lh, lw, nh, nw); return STCN_E_INVALID; }
+    if (t0 < 0 || t1 > T || t0 >= t1) { set_error("%s: frames [%d, %d) are not a non-empty range inside [0, %d)", who, t0, t1, T); return STCN_E_INVALID; }
+    const size_t hw = (size_t)H * W;
+    void *scratch = j_only ? nullptr : (char *)scratch_dev + (labels ? label_scratch_bytes(k, t0, H, W) : t0 * hw);      // the scratch of frame t0
+    round_score_launch(masks_dev + (size_t)t0 * nh * nw, nh, nw, lh, lw, gt_dev + t0 * hw, annotated_dev + t0, flags_dev, labels ? k : 0, t1 - t0, H, W,
+                       j_only ? -1 : bound_radius(H, W), no_object, gen_dev + t0 * hw, scratch, counts_dev + (size_t)t0 * 6, T, object_quality_dev,
+                       quality_dev, select_dev, (hipStream_t)stream, t0);
     HIPCHK(hipGetLastError());
     return STCN_OK;
 }
@@ -446,73 +495,16 @@ int stcn_metrics_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pr
 int stcn_metrics_round(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev, const uint8_t *annotated_dev,
                        const uint8_t *noobj_dev, int T, int H, int W, int t0, int t1, int j_only, double no_object, uint8_t *gen_dev, uint8_t *scratch_dev,
                        int32_t *counts_dev, double *quality_dev, int32_t *select_dev) {
-    if (!masks_dev || !gt_dev || !annotated_dev || !noobj_dev || !gen_dev || !counts_dev || !quality_dev || !select_dev || (!j_only && !scratch_dev) ||
-        T < 1 || H < 2 || W < 2 || lh < 0 || lw < 0 || lh + H > nh || lw + W > nw || t0 < 0 || t1 > T || t0 >= t1) {
-        set_error("stcn_metrics_round: bad arguments");
-        return STCN_E_INVALID;
-    }
-    const int radius = j_only ? -1 : (int)std::ceil(0.008 * std::sqrt((double)H * H + (double)W * W));      // interactions/metrics.py:119-120
-    // frames [t0, t1): composed and counted now; the counts (and gen) of the other frames are the caller's from earlier rounds
-    const size_t hw = (size_t)H * W;
-    round_score_launch(masks_dev + (size_t)t0 * nh * nw, nh, nw, lh, lw, gt_dev + t0 * hw, annotated_dev + t0, noobj_dev, t1 - t0, H, W, radius, no_object,
-                       gen_dev + t0 * hw, scratch_dev, counts_dev + (size_t)t0 * 6, T, quality_dev, select_dev, (hipStream_t)stream, t0);
-    HIPCHK(hipGetLastError());
-    return STCN_OK;
-}
-
-// ---- label maps of k objects: every argument is checked before any device call -------------------------------------------------------
-static bool objects_ok(const char *who, int k, int T, int H, int W) {
-    if (k < 1 || k > STCN_MAX_OBJECTS) { set_error("%s: k = %d outside 1..%d (STCN_MAX_OBJECTS)", who, k, STCN_MAX_OBJECTS); return false; }
-    if (T < 1 || H < 2 || W < 2) { set_error("%s: bad shape (T >= 1, H, W >= 2 required; T=%d H=%d W=%d)", who, T, H, W); return false; }
-    return true;
-}
-
-static int bound_radius(int H, int W) { return (int)std::ceil(0.008 * std::sqrt((double)H * H + (double)W * W)); }      // interactions/metrics.py:119-120
-
-int stcn_metrics_objects_scratch(int k, int T, int H, int W, int64_t *bytes) {
-    if (!objects_ok("stcn_metrics_objects_scratch", k, T, H, W)) return STCN_E_INVALID;
-    if (!bytes) { set_error("stcn_metrics_objects_scratch: null pointer"); return STCN_E_INVALID; }
-    *bytes = (int64_t)label_scratch_bytes(k, T, H, W);
-    return STCN_OK;
-}
-
-int stcn_metrics_objects_jf_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int k, int T, int H, int W, int32_t *counts_dev,
-                                   void *scratch_dev) {
-    if (!objects_ok("stcn_metrics_objects_jf_counts", k, T, H, W)) return STCN_E_INVALID;
-    if (!gt_dev || !pred_dev || !counts_dev || !scratch_dev) { set_error("stcn_metrics_objects_jf_counts: null pointer"); return STCN_E_INVALID; }
-    label_counts_launch(gt_dev, pred_dev, k, T, H, W, bound_radius(H, W), scratch_dev, counts_dev, T, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return STCN_OK;
-}
-
-int stcn_metrics_objects_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int k, int T, int H, int W, int32_t *counts_dev) {
-    if (!objects_ok("stcn_metrics_objects_j_counts", k, T, H, W)) return STCN_E_INVALID;
-    if (!gt_dev || !pred_dev || !counts_dev) { set_error("stcn_metrics_objects_j_counts: null pointer"); return STCN_E_INVALID; }
-    label_counts_launch(gt_dev, pred_dev, k, T, H, W, -1, nullptr, counts_dev, T, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return STCN_OK;
+    return metrics_round("stcn_metrics_round", false, stream, masks_dev, nh, nw, lh, lw, gt_dev, annotated_dev, noobj_dev, 0, T, H, W, t0, t1, j_only,
+                         no_object, gen_dev, scratch_dev, counts_dev, nullptr, quality_dev, select_dev);
 }
 
 int stcn_metrics_objects_round(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev,
                                const uint8_t *annotated_dev, const uint8_t *present_dev, int k, int T, int H, int W, int t0, int t1, int j_only,
                                double no_object, uint8_t *gen_dev, void *scratch_dev, int32_t *counts_dev, double *object_quality_dev,
                                double *quality_dev, int32_t *select_dev) {
-    const char *who = "stcn_metrics_objects_round";
-    if (!objects_ok(who, k, T, H, W)) return STCN_E_INVALID;
-    if (!masks_dev || !gt_dev || !annotated_dev || !present_dev || !gen_dev || !counts_dev || !object_quality_dev || !quality_dev || !select_dev ||
-        (!j_only && !scratch_dev)) {
-        set_error("%s: null pointer", who);
-        return STCN_E_INVALID;
-    }
-    if (lh < 0 || lw < 0 || lh + H > nh || lw + W > nw) { set_error("%s: the %d x %d crop at (%d, %d) leaves the %d x %d tensor", who, H, W, lh, lw, nh, nw); return STCN_E_INVALID; }
-    if (t0 < 0 || t1 > T || t0 >= t1) { set_error("%s: frames [%d, %d) are not a non-empty range inside [0, %d)", who, t0, t1, T); return STCN_E_INVALID; }
-    const size_t hw = (size_t)H * W;
-    void *bsets = j_only ? nullptr : (char *)scratch_dev + label_scratch_bytes(k, t0, H, W);          // the sets of frame t0
-    label_round_score_launch(masks_dev + (size_t)t0 * nh * nw, nh, nw, lh, lw, gt_dev + t0 * hw, annotated_dev + t0, present_dev, k, t1 - t0, H, W,
-                             j_only ? -1 : bound_radius(H, W), no_object, gen_dev + t0 * hw, bsets, counts_dev + (size_t)t0 * 6, T, object_quality_dev,
-                             quality_dev, select_dev, (hipStream_t)stream, t0);
-    HIPCHK(hipGetLastError());
-    return STCN_OK;
+    return metrics_round("stcn_metrics_objects_round", true, stream, masks_dev, nh, nw, lh, lw, gt_dev, annotated_dev, present_dev, k, T, H, W, t0, t1,
+                         j_only, no_object, gen_dev, scratch_dev, counts_dev, object_quality_dev, quality_dev, select_dev);
 }
 
 int stcn_bench_mfma_rate(void *stream, int ms_target, float *tflops, float *ms_out) {

@@ -285,11 +285,6 @@ void pack_fusion_input_launch(const float *img4, const float *prev, const float 
 // (intersection, union, gt boundary px, pred boundary px, matched gt boundary px, matched pred boundary px)
 void jf_counts_launch(const uint8_t *gt, const uint8_t *pred, int T, int H, int W, int radius, uint8_t *bmap,
                       int *counts, hipStream_t s);
-// one annotation round scored on the device: gen = engine mask / GT on annotated frames, J or J&F counts, fp64 quality per frame, arg-min
-// (pointers at the first of the Tn frames to recount; quality / arg-min over the T_all frames of the clip, t0 = index of that first frame)
-void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *noobj,
-                        int Tn, int H, int W, int radius, double no_object, uint8_t *gen, uint8_t *bmap, int *counts, int T_all, double *quality,
-                        int *select, hipStream_t s, int t0);
 
 // ---- the same for LABEL MAPS of k objects (0 = background, o in 1..k = object o; a label above k counts as background) ----
 // counts [k][T_all][6]: per object the six integers jf_counts_launch gives for the binary masks (gt == o), (pred == o).  The boundary scratch
@@ -299,11 +294,13 @@ size_t label_scratch_bytes(int k, int T, int H, int W);
 // gt / pred / bsets / counts point at the first of the Tn frames to count; T_all = frames per object in counts (the object stride)
 void label_counts_launch(const uint8_t *gt, const uint8_t *pred, int k, int Tn, int H, int W, int radius, void *bsets, int *counts, int T_all,
                          hipStream_t s);
-// a k-object annotation round: compose, counts, per-object quality [k][T_all], frame quality [T_all] (mean over the objects present in the
-// ground truth of the frame, ascending o) and its arg-min; pointer conventions as round_score_launch, present = uint8 [k][T_all]
-void label_round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated,
-                              const uint8_t *present, int k, int Tn, int H, int W, int radius, double no_object, uint8_t *gen, void *bsets,
-                              int *counts, int T_all, double *object_quality, double *quality, int *select, hipStream_t s, int t0);
+// One annotation round scored on the device: gen = engine mask / GT on annotated frames, J or J&F counts, fp64 quality per frame, arg-min.
+// k = 0: binary masks (flags = noobj [T_all], scratch = bmap, object_quality unused); k >= 1: label maps of k objects (flags = present
+// [k][T_all], scratch = bsets): per-object quality [k][T_all], frame quality = mean over the objects present in the frame, ascending o.
+// Pointers at the first of the Tn frames to recount; quality / arg-min over the T_all frames of the clip, t0 = index of that first frame.
+void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *flags, int k,
+                        int Tn, int H, int W, int radius, double no_object, uint8_t *gen, void *scratch, int *counts, int T_all,
+                        double *object_quality, double *quality, int *select, hipStream_t s, int t0);
 
 // pure fp32-MFMA load (no memory traffic): launches `grid` workgroups of 12 waves x iters x 12 MFMAs, returns the FLOP of the launch
 double mfma_probe_launch(float *out, int grid, int iters, hipStream_t s);

@@ -10,8 +10,6 @@
 
 namespace stcn {
 
-void jf_counts_launch(const uint8_t *gt, const uint8_t *pred, int T, int H, int W, int radius, uint8_t *bmap, int *counts, hipStream_t s);
-
 // Counting: a thread visits PPT pixels (a wave 64 consecutive pixels per step: coalesced byte loads), keeps its counters in registers
 // and the wave adds them up ONCE at the end - one integer atomic per wave and counter when the wave's 64 x PPT pixels lie inside one
 // frame (all but the ~T waves that straddle a frame boundary, which fall back to one atomic per pixel).  Round 3 issued one atomic per
@@ -19,32 +17,88 @@ void jf_counts_launch(const uint8_t *gt, const uint8_t *pred, int T, int H, int 
 // annotation round of the eval driver; a per-pixel atomicAdd before that 49 ms.
 static constexpr int PPT = 16;
 
+// The walk of the four counting kernels: wave w of workgroup b owns the 64 x PPT pixels from first_pixel(w) on, of the n = T x H x W of
+// the clip.  A pixel is handed to the kernel body with its index i in the clip and its frame t; its row and column cost an integer
+// division, so they are computed where the body asks for them (the match kernels do only at boundary pixels), not for every pixel.
+struct Pixel {
+    long i;
+    int t, rem, W;         // rem: index inside frame t
+    __device__ __forceinline__ int y() const { return rem / W; }
+    __device__ __forceinline__ int x() const { return rem - y() * W; }
+};
+
+struct WaveWalk {
+    long hw, n, base;      // pixels per frame, pixels in all, first pixel of this wave
+    int W, lane, t0;       // t0: the frame of `base`
+    bool one_frame;        // wave-uniform: every pixel of the wave lies in frame t0 (false for a wave past the end, which visits nothing)
+    static __device__ __forceinline__ long first_pixel(int wave) { return ((long)blockIdx.x * 4 + wave) * (64L * PPT); }
+    __device__ __forceinline__ WaveWalk(int T, int H, int W_) : hw((long)H * W_), n(T * hw), base(first_pixel(threadIdx.x >> 6)), W(W_), lane(threadIdx.x & 63) {
+        t0 = (int)(base / hw);
+        one_frame = base < n && (int)((min(base + 64L * PPT, n) - 1) / hw) == t0;
+    }
+    template <typename Body> __device__ __forceinline__ void for_each(Body &&body) const {
+        for (int j = 0; j < PPT; ++j) {
+            const long i = base + j * 64L + lane;
+            if (i >= n) break;
+            const int t = one_frame ? t0 : (int)(i / hw);
+            body(Pixel{i, t, (int)(i - t * hw), W});
+        }
+    }
+};
+
+// The disk of radius r around (y, x), clipped to the H x W frame: visit(index inside the frame) for its elements, rows from the centre
+// outwards (0, -1, +1, -2, ...), until done() says - before a row - that everything wanted was found: the two boundaries usually run
+// close to each other, the scan ends early.
+template <typename Visit, typename Done>
+__device__ __forceinline__ void disk_scan(int y, int x, int H, int W, int r, Visit &&visit, Done &&done) {
+    for (int d = 0; d <= 2 * r && !done(); ++d) {
+        const int dy = (d & 1) ? -((d + 1) >> 1) : (d >> 1);
+        const int yy = y + dy;
+        if ((unsigned)yy >= (unsigned)H) continue;
+        int hx = 0;                                           // half width of the disk at this row: largest dx with dx^2 + dy^2 <= r^2
+        while ((hx + 1) * (hx + 1) + dy * dy <= r * r) ++hx;
+        const int x0 = max(x - hx, 0), x1 = min(x + hx, W - 1);
+        const long row = (long)yy * W;
+        for (int xx = x0; xx <= x1; ++xx) visit(row + xx);
+    }
+}
+
+// ---- counters: two policies, on purpose -----------------------------------------------------------------------------------------------
+// Binary masks: all pixels of a frame add to the same six counters, so a thread counts in REGISTERS, the wave adds its lanes up once
+// (wave_sum) and lane 0 issues one global atomic per counter.  Label maps: a pixel adds to the counters of the few objects it touches,
+// in a [k][6] table per wave in LDS (LabelCounters, flush_tables) - registers would be k x 6 per lane.  The binary entry points are NOT
+// routed through the label kernels with k = 1: every lane of a wave would then add to the same LDS word, and what those same-address
+// LDS atomics cost beside one register add per lane has never been measured.  In both, the ~T waves that lie across a frame boundary
+// add per pixel to global memory.
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
 
+// n register counters of a wave inside one frame -> the frame's counters from `c` on (lane 0, the non-zero ones)
+template <int N> __device__ __forceinline__ void wave_flush(const WaveWalk &w, const int (&v)[N], int *__restrict__ c) {
+    if (!w.one_frame) return;
+    int sum[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) sum[e] = wave_sum(v[e]);
+    if (w.lane != 0) return;
+#pragma unroll
+    for (int e = 0; e < N; ++e)
+        if (sum[e]) atomicAdd(&c[e], sum[e]);
+}
+
 // bit0 = gt boundary, bit1 = pred boundary.  j_only: intersection / union only (bmap untouched)
 __global__ __launch_bounds__(256) void jf_boundary_kernel(const uint8_t *__restrict__ gt, const uint8_t *__restrict__ pr, int T, int H, int W,
                                                           uint8_t *__restrict__ bmap, int *__restrict__ counts, int j_only) {
-    const long hw = (long)H * W, n = T * hw;
-    const int lane = threadIdx.x & 63;
-    const long base = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64L * PPT);          // first pixel of this wave
-    if (base >= n) return;
-    const long last = min(base + 64L * PPT, n) - 1;
-    const int t0 = (int)(base / hw);
-    const bool one_frame = (int)(last / hw) == t0;                                       // wave-uniform
-    int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    for (int j = 0; j < PPT; ++j) {
-        const long i = base + j * 64L + lane;
-        if (i >= n) break;
-        const int t = one_frame ? t0 : (int)(i / hw);
-        const int rem = (int)(i - t * hw);
+    const WaveWalk walk(T, H, W);
+    int c[4] = {0, 0, 0, 0};               // inter, union, n_gt_b, n_fg_b
+    walk.for_each([&](const Pixel &px) {
+        const long i = px.i;
         const int g = gt[i] != 0, p = pr[i] != 0;
         int bg = 0, bp = 0;
         if (!j_only) {
-            const int y = rem / W, x = rem - y * W;
+            const int y = px.y(), x = px.x();
             auto bnd = [&](const uint8_t *seg, int s) -> int {
                 const uint8_t *q = seg + i;
                 if (y < H - 1 && x < W - 1) {
@@ -59,148 +113,36 @@ __global__ __launch_bounds__(256) void jf_boundary_kernel(const uint8_t *__restr
             bp = bnd(pr, p);
             bmap[i] = (uint8_t)(bg | (bp << 1));
         }
-        if (one_frame) { c0 += g & p; c1 += g | p; c2 += bg; c3 += bp; }
+        if (walk.one_frame) { c[0] += g & p; c[1] += g | p; c[2] += bg; c[3] += bp; }
         else {                                                                           // a wave across a frame boundary: per pixel
-            int *c = counts + t * 6;
-            if (g & p) atomicAdd(&c[0], 1);
-            if (g | p) atomicAdd(&c[1], 1);
-            if (bg) atomicAdd(&c[2], 1);
-            if (bp) atomicAdd(&c[3], 1);
+            int *ct = counts + px.t * 6;
+            if (g & p) atomicAdd(&ct[0], 1);
+            if (g | p) atomicAdd(&ct[1], 1);
+            if (bg) atomicAdd(&ct[2], 1);
+            if (bp) atomicAdd(&ct[3], 1);
         }
-    }
-    if (one_frame) {
-        c0 = wave_sum(c0); c1 = wave_sum(c1); c2 = wave_sum(c2); c3 = wave_sum(c3);
-        int *c = counts + t0 * 6;          // inter, union, n_gt_b, n_fg_b, gt_match, fg_match
-        if (lane == 0) {
-            if (c0) atomicAdd(&c[0], c0);
-            if (c1) atomicAdd(&c[1], c1);
-            if (c2) atomicAdd(&c[2], c2);
-            if (c3) atomicAdd(&c[3], c3);
-        }
-    }
+    });
+    wave_flush(walk, c, counts + walk.t0 * 6);
 }
 
 __global__ __launch_bounds__(256) void jf_match_kernel(const uint8_t *__restrict__ bmap, int T, int H, int W, int r, int *__restrict__ counts) {
-    const long hw = (long)H * W, n = T * hw;
-    const int lane = threadIdx.x & 63;
-    const long base = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64L * PPT);
-    if (base >= n) return;
-    const long last = min(base + 64L * PPT, n) - 1;
-    const int t0 = (int)(base / hw);
-    const bool one_frame = (int)(last / hw) == t0;
-    int c4 = 0, c5 = 0;
-    for (int j = 0; j < PPT; ++j) {
-        const long i = base + j * 64L + lane;
-        if (i >= n) break;
-        const int me = bmap[i];
-        if (!me) continue;                                    // only boundary pixels (a few thousand per frame) scan the disk
-        const int t = one_frame ? t0 : (int)(i / hw);
-        const int rem = (int)(i - t * hw);
-        const int y = rem / W, x = rem - y * W;
-        const uint8_t *b = bmap + (long)t * hw;
+    const WaveWalk walk(T, H, W);
+    int c[2] = {0, 0};                     // gt_match, fg_match
+    walk.for_each([&](const Pixel &px) {
+        const int me = bmap[px.i];
+        if (!me) return;                                      // only boundary pixels (a few thousand per frame) scan the disk
+        const uint8_t *b = bmap + (long)px.t * walk.hw;
         const int want = ((me & 1) ? 2 : 0) | ((me & 2) ? 1 : 0);
         int other = 0;                                        // bits of the OTHER map found inside the disk
-        // rows from the centre outwards (0, -1, +1, -2, ...): the two boundaries usually run close to each other, the scan ends early
-        for (int k = 0; k <= 2 * r && (other & want) != want; ++k) {
-            const int dy = (k & 1) ? -((k + 1) >> 1) : (k >> 1);
-            const int yy = y + dy;
-            if ((unsigned)yy >= (unsigned)H) continue;
-            int hx = 0;                                       // half width of the disk at this row: largest dx with dx^2 + dy^2 <= r^2
-            while ((hx + 1) * (hx + 1) + dy * dy <= r * r) ++hx;
-            const int x0 = max(x - hx, 0), x1 = min(x + hx, W - 1);
-            const uint8_t *row = b + (long)yy * W;
-            for (int xx = x0; xx <= x1; ++xx) other |= row[xx];
-        }
+        disk_scan(px.y(), px.x(), H, W, r, [&](long e) { other |= b[e]; }, [&] { return (other & want) == want; });
         const int m4 = (me & 1) && (other & 2), m5 = (me & 2) && (other & 1);
-        if (one_frame) { c4 += m4; c5 += m5; }
+        if (walk.one_frame) { c[0] += m4; c[1] += m5; }
         else {
-            if (m4) atomicAdd(&counts[t * 6 + 4], 1);         // gt boundary pixel inside dilated pred boundary
-            if (m5) atomicAdd(&counts[t * 6 + 5], 1);         // pred boundary pixel inside dilated gt boundary
+            if (m4) atomicAdd(&counts[px.t * 6 + 4], 1);      // gt boundary pixel inside dilated pred boundary
+            if (m5) atomicAdd(&counts[px.t * 6 + 5], 1);      // pred boundary pixel inside dilated gt boundary
         }
-    }
-    if (one_frame) {
-        c4 = wave_sum(c4); c5 = wave_sum(c5);
-        if (lane == 0) {
-            if (c4) atomicAdd(&counts[t0 * 6 + 4], c4);
-            if (c5) atomicAdd(&counts[t0 * 6 + 5], c5);
-        }
-    }
-}
-
-// ---- one annotation round on the device (round 6): compose -> counts -> quality + selection ------------------------------------------
-// gen[t] = the engine's mask of frame t (cropped out of the padded [T][nh][nw] tensor, non-zero = object), or the ground truth where the frame
-// is annotated (interactions/eval.py:57-60: annotated frames count with their GT mask).  gen is what util/fq_dataset.py:64-84 saves as a state.
-__global__ __launch_bounds__(256) void round_compose_kernel(const uint8_t *__restrict__ masks, int nh, int nw, int lh, int lw,
-                                                            const uint8_t *__restrict__ gt, const uint8_t *__restrict__ annotated, int T, int H, int W,
-                                                            uint8_t *__restrict__ gen) {
-    const long hw = (long)H * W, n = T * hw;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int t = (int)(i / hw);
-        const int rem = (int)(i - t * hw);
-        const int y = rem / W, x = rem - y * W;
-        gen[i] = annotated[t] ? (uint8_t)(gt[i] != 0) : (uint8_t)(masks[((long)t * nh + y + lh) * nw + x + lw] != 0);
-    }
-}
-
-// quality[t] in fp64 with the operations, and their order, of the host path (eva_vos_amd/metrics.py::_scores_from_counts, itself the
-// reference's interactions/metrics.py:141-158 / eval.py:62-79): J = inter / union (0 when the union is empty), F = 2 p r / (p + r) with the
-// reference's special cases, J&F = 0.5 (J + F); frames whose ground truth is empty get the NO_OBJECT token.  IEEE division / multiplication /
-// addition are correctly rounded on the device as on the host, so the values - and therefore the arg-min (first index of the minimum, as
-// numpy.argmin) - are bit-identical to the host path's.  One workgroup; T <= a few hundred.
-__device__ __forceinline__ double quality_of(const int *__restrict__ c, int j_only) {
-    const double j = c[1] == 0 ? 0.0 : __ddiv_rn((double)c[0], (double)c[1]);
-    if (j_only) return j;
-    const int n_gt = c[2], n_fg = c[3];
-    double p, r;
-    if (n_fg == 0 && n_gt > 0) { p = 1.0; r = 0.0; }
-    else if (n_fg > 0 && n_gt == 0) { p = 0.0; r = 1.0; }
-    else if (n_fg == 0 && n_gt == 0) { p = 1.0; r = 1.0; }
-    else { p = __ddiv_rn((double)c[5], (double)n_fg); r = __ddiv_rn((double)c[4], (double)n_gt); }
-    const double s = __dadd_rn(p, r);
-    const double f = s == 0.0 ? 0.0 : __ddiv_rn(__dmul_rn(__dmul_rn(2.0, p), r), s);
-    return __dmul_rn(0.5, __dadd_rn(j, f));
-}
-
-// first index of the minimum over the workgroup's 256 (best, besti) pairs, each the first minimum of its thread's ascending subsequence
-__device__ __forceinline__ void block_argmin(double best, int besti, int *__restrict__ select) {
-    __shared__ double sv[256];
-    __shared__ int si[256];
-    sv[threadIdx.x] = best; si[threadIdx.x] = besti;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double v = sv[threadIdx.x + o]; const int i2 = si[threadIdx.x + o];
-            if (v < sv[threadIdx.x] || (v == sv[threadIdx.x] && i2 < si[threadIdx.x])) { sv[threadIdx.x] = v; si[threadIdx.x] = i2; }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) select[0] = si[0];
-}
-
-__global__ __launch_bounds__(256) void round_quality_kernel(const int *__restrict__ counts, const uint8_t *__restrict__ noobj, int T, int j_only,
-                                                            double no_object, double *__restrict__ quality, int *__restrict__ select) {
-    double best = __builtin_inf();
-    int besti = 0x7fffffff;
-    for (int t = threadIdx.x; t < T; t += 256) {
-        double q = quality_of(counts + t * 6, j_only);
-        if (noobj[t]) q = no_object;
-        quality[t] = q;
-        if (q < best) { best = q; besti = t; }                               // ascending t per thread: the first minimum of its subsequence
-    }
-    block_argmin(best, besti, select);
-}
-
-// masks / gt / annotated / gen / counts point at the FIRST of the Tn frames to (re)compose and count; the quality and the arg-min cover all
-// T_all frames of the clip, whose counts start Tn0 = (counts - counts_all) / 6 frames earlier: the caller passes counts of frame t0 and T_all,
-// noobj and quality are whole-clip arrays
-void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *noobj,
-                        int Tn, int H, int W, int radius, double no_object, uint8_t *gen, uint8_t *bmap, int *counts, int T_all, double *quality,
-                        int *select, hipStream_t s, int t0) {
-    const long n = (long)Tn * H * W;
-    const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(round_compose_kernel, dim3(blocks), dim3(256), 0, s, masks, nh, nw, lh, lw, gt, annotated, Tn, H, W, gen);
-    jf_counts_launch(gt, gen, Tn, H, W, radius, bmap, counts, s);
-    hipLaunchKernelGGL(round_quality_kernel, dim3(1), dim3(256), 0, s, counts - (long)t0 * 6, noobj, T_all, radius < 0 ? 1 : 0, no_object, quality, select);
+    });
+    wave_flush(walk, c, counts + walk.t0 * 6 + 4);
 }
 
 void jf_counts_launch(const uint8_t *gt, const uint8_t *pred, int T, int H, int W, int radius, uint8_t *bmap,
@@ -250,7 +192,7 @@ __device__ __forceinline__ void flush_tables(const int (*tab)[LT], int k, long h
         const int w = e / (k * 6), r = e - w * (k * 6);
         const int v = tab[w][r];
         if (!v) continue;
-        const int t = (int)((((long)blockIdx.x * 4 + w) * (64L * PPT)) / hw);
+        const int t = (int)(WaveWalk::first_pixel(w) / hw);
         atomicAdd(&counts[((long)(r / 6) * T_all + t) * 6 + r % 6], v);
     }
 }
@@ -261,41 +203,33 @@ __global__ __launch_bounds__(256) void label_boundary_kernel(const uint8_t *__re
     __shared__ int tab[4][LT];
     for (int e = threadIdx.x; e < 4 * LT; e += 256) (&tab[0][0])[e] = 0;
     __syncthreads();
-    const long hw = (long)H * W, n = T * hw;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long base = ((long)blockIdx.x * 4 + wv) * (64L * PPT);                          // first pixel of this wave
-    if (base < n) {
-        const long last = min(base + 64L * PPT, n) - 1;
-        const int t0 = (int)(base / hw);
-        const LabelCounters cn{tab[wv], counts, T_all, (int)(last / hw) == t0};
-        for (int j = 0; j < PPT; ++j) {
-            const long i = base + j * 64L + lane;
-            if (i >= n) break;
-            const int t = cn.one_frame ? t0 : (int)(i / hw);
-            const int g = label_of(gt[i], k), p = label_of(pr[i], k);
-            if (!j_only) {
-                const int rem = (int)(i - t * hw);
-                const int y = rem / W, x = rem - y * W;
-                auto bnd = [&](const uint8_t *seg, int s) -> unsigned {                      // _seg2bmap for every object at once
-                    const uint8_t *q = seg + i;
-                    unsigned b = 0;
-                    auto differ = [&](uint8_t v) { const int nb = label_of(v, k); if (nb != s) b |= bit_of(s) | bit_of(nb); };
-                    if (y < H - 1 && x < W - 1) { differ(q[1]); differ(q[W]); differ(q[W + 1]); }
-                    else if (y == H - 1 && x < W - 1) differ(q[1]);
-                    else if (x == W - 1 && y < H - 1) differ(q[W]);
-                    return b;
-                };
-                const unsigned bg = bnd(gt, g), bp = bnd(pr, p);
-                bsets[i] = BSet<Wd>{(Wd)bg, (Wd)bp};
-                cn.add_set(bg, t, 2);
-                cn.add_set(bp, t, 3);
-            }
-            if (g) { if (g == p) cn.add(g - 1, t, 0); cn.add(g - 1, t, 1); }                // union of o: every pixel that is o in either map
-            if (p && p != g) cn.add(p - 1, t, 1);
+    const WaveWalk walk(T, H, W);
+    const LabelCounters cn{tab[threadIdx.x >> 6], counts, T_all, walk.one_frame};
+    walk.for_each([&](const Pixel &px) {
+        const long i = px.i;
+        const int t = px.t;
+        const int g = label_of(gt[i], k), p = label_of(pr[i], k);
+        if (!j_only) {
+            const int y = px.y(), x = px.x();
+            auto bnd = [&](const uint8_t *seg, int s) -> unsigned {                      // _seg2bmap for every object at once
+                const uint8_t *q = seg + i;
+                unsigned b = 0;
+                auto differ = [&](uint8_t v) { const int nb = label_of(v, k); if (nb != s) b |= bit_of(s) | bit_of(nb); };
+                if (y < H - 1 && x < W - 1) { differ(q[1]); differ(q[W]); differ(q[W + 1]); }
+                else if (y == H - 1 && x < W - 1) differ(q[1]);
+                else if (x == W - 1 && y < H - 1) differ(q[W]);
+                return b;
+            };
+            const unsigned bg = bnd(gt, g), bp = bnd(pr, p);
+            bsets[i] = BSet<Wd>{(Wd)bg, (Wd)bp};
+            cn.add_set(bg, t, 2);
+            cn.add_set(bp, t, 3);
         }
-    }
+        if (g) { if (g == p) cn.add(g - 1, t, 0); cn.add(g - 1, t, 1); }                // union of o: every pixel that is o in either map
+        if (p && p != g) cn.add(p - 1, t, 1);
+    });
     __syncthreads();
-    flush_tables(tab, k, hw, counts, T_all);
+    flush_tables(tab, k, walk.hw, counts, T_all);
 }
 
 template <typename Wd>
@@ -304,78 +238,20 @@ __global__ __launch_bounds__(256) void label_match_kernel(const BSet<Wd> *__rest
     __shared__ int tab[4][LT];
     for (int e = threadIdx.x; e < 4 * LT; e += 256) (&tab[0][0])[e] = 0;
     __syncthreads();
-    const long hw = (long)H * W, n = T * hw;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const long base = ((long)blockIdx.x * 4 + wv) * (64L * PPT);
-    if (base < n) {
-        const long last = min(base + 64L * PPT, n) - 1;
-        const int t0 = (int)(base / hw);
-        const LabelCounters cn{tab[wv], counts, T_all, (int)(last / hw) == t0};
-        for (int j = 0; j < PPT; ++j) {
-            const long i = base + j * 64L + lane;
-            if (i >= n) break;
-            const BSet<Wd> me = bsets[i];
-            if (!(me.g | me.p)) continue;                     // only boundary pixels scan the disk
-            const int t = cn.one_frame ? t0 : (int)(i / hw);
-            const int rem = (int)(i - t * hw);
-            const int y = rem / W, x = rem - y * W;
-            const BSet<Wd> *b = bsets + (long)t * hw;
-            unsigned og = 0, op = 0;                          // objects whose gt / pred boundary lies inside the disk
-            for (int d = 0; d <= 2 * r && ((op & me.g) != me.g || (og & me.p) != me.p); ++d) {       // rows from the centre outwards
-                const int dy = (d & 1) ? -((d + 1) >> 1) : (d >> 1);
-                const int yy = y + dy;
-                if ((unsigned)yy >= (unsigned)H) continue;
-                int hx = 0;
-                while ((hx + 1) * (hx + 1) + dy * dy <= r * r) ++hx;
-                const int x0 = max(x - hx, 0), x1 = min(x + hx, W - 1);
-                const BSet<Wd> *row = b + (long)yy * W;
-                for (int xx = x0; xx <= x1; ++xx) { const BSet<Wd> v = row[xx]; og |= v.g; op |= v.p; }
-            }
-            cn.add_set(me.g & op, t, 4);                      // object o's gt boundary pixel inside ITS dilated pred boundary
-            cn.add_set(me.p & og, t, 5);
-        }
-    }
+    const WaveWalk walk(T, H, W);
+    const LabelCounters cn{tab[threadIdx.x >> 6], counts, T_all, walk.one_frame};
+    walk.for_each([&](const Pixel &px) {
+        const BSet<Wd> me = bsets[px.i];
+        if (!(me.g | me.p)) return;                           // only boundary pixels scan the disk
+        const BSet<Wd> *b = bsets + (long)px.t * walk.hw;
+        unsigned og = 0, op = 0;                              // objects whose gt / pred boundary lies inside the disk
+        disk_scan(px.y(), px.x(), H, W, r, [&](long e) { const BSet<Wd> v = b[e]; og |= v.g; op |= v.p; },
+                  [&] { return (op & me.g) == me.g && (og & me.p) == me.p; });
+        cn.add_set(me.g & op, px.t, 4);                       // object o's gt boundary pixel inside ITS dilated pred boundary
+        cn.add_set(me.p & og, px.t, 5);
+    });
     __syncthreads();
-    flush_tables(tab, k, hw, counts, T_all);
-}
-
-__global__ __launch_bounds__(256) void label_compose_kernel(const uint8_t *__restrict__ masks, int nh, int nw, int lh, int lw,
-                                                            const uint8_t *__restrict__ gt, const uint8_t *__restrict__ annotated, int k, int T, int H,
-                                                            int W, uint8_t *__restrict__ gen) {
-    const long hw = (long)H * W, n = T * hw;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int t = (int)(i / hw);
-        const int rem = (int)(i - t * hw);
-        const int y = rem / W, x = rem - y * W;
-        gen[i] = (uint8_t)label_of(annotated[t] ? gt[i] : masks[((long)t * nh + y + lh) * nw + x + lw], k);
-    }
-}
-
-// object_quality[o][t] as round_quality_kernel computes it from the counts of object o (NO_OBJECT where present[o][t] is 0), quality[t] = the
-// mean over the objects present in frame t - added in ascending o, correctly rounded, then one division by their number - or NO_OBJECT when
-// there is none; select = first index of the minimum of quality.  The host restatement is metrics.label_round_quality.
-__global__ __launch_bounds__(256) void label_quality_kernel(const int *__restrict__ counts, const uint8_t *__restrict__ present, int k, int T, int j_only,
-                                                            double no_object, double *__restrict__ object_quality, double *__restrict__ quality,
-                                                            int *__restrict__ select) {
-    double best = __builtin_inf();
-    int besti = 0x7fffffff;
-    for (int t = threadIdx.x; t < T; t += 256) {
-        double sum = 0.0;
-        int cnt = 0;
-        for (int o = 0; o < k; ++o) {
-            double q = no_object;
-            if (present[o * T + t]) {
-                q = quality_of(counts + ((long)o * T + t) * 6, j_only);
-                sum = __dadd_rn(sum, q);
-                ++cnt;
-            }
-            object_quality[o * T + t] = q;
-        }
-        const double q = cnt ? __ddiv_rn(sum, (double)cnt) : no_object;
-        quality[t] = q;
-        if (q < best) { best = q; besti = t; }
-    }
-    block_argmin(best, besti, select);
+    flush_tables(tab, k, walk.hw, counts, T_all);
 }
 
 size_t label_scratch_bytes(int k, int T, int H, int W) { return (size_t)T * H * W * (k <= 8 ? sizeof(BSet<uint8_t>) : sizeof(BSet<uint32_t>)); }
@@ -397,15 +273,106 @@ void label_counts_launch(const uint8_t *gt, const uint8_t *pred, int k, int Tn, 
     else label_counts_kernels<uint32_t>(gt, pred, k, Tn, H, W, radius, bsets, counts, T_all, blocks, s);
 }
 
-void label_round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated,
-                              const uint8_t *present, int k, int Tn, int H, int W, int radius, double no_object, uint8_t *gen, void *bsets,
-                              int *counts, int T_all, double *object_quality, double *quality, int *select, hipStream_t s, int t0) {
+// ---- one annotation round on the device (round 6): compose -> counts -> quality + selection ------------------------------------------
+// gen[t] = the engine's mask of frame t (cropped out of the padded [T][nh][nw] tensor), or the ground truth where the frame is annotated
+// (interactions/eval.py:57-60: annotated frames count with their GT mask).  gen is what util/fq_dataset.py:64-84 saves as a state.
+// Binary masks: non-zero = object; LABELS: label maps of k objects.
+template <bool LABELS>
+__global__ __launch_bounds__(256) void round_compose_kernel(const uint8_t *__restrict__ masks, int nh, int nw, int lh, int lw,
+                                                            const uint8_t *__restrict__ gt, const uint8_t *__restrict__ annotated, int k, int T, int H,
+                                                            int W, uint8_t *__restrict__ gen) {
+    const long hw = (long)H * W, n = T * hw;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int t = (int)(i / hw);
+        const int rem = (int)(i - t * hw);
+        const int y = rem / W, x = rem - y * W;
+        const uint8_t v = annotated[t] ? gt[i] : masks[((long)t * nh + y + lh) * nw + x + lw];
+        gen[i] = LABELS ? (uint8_t)label_of(v, k) : (uint8_t)(v != 0);
+    }
+}
+
+// quality[t] in fp64 with the operations, and their order, of the host path (eva_vos_amd/metrics.py::_scores_from_counts, itself the
+// reference's interactions/metrics.py:141-158 / eval.py:62-79): J = inter / union (0 when the union is empty), F = 2 p r / (p + r) with the
+// reference's special cases, J&F = 0.5 (J + F); frames whose ground truth is empty get the NO_OBJECT token.  IEEE division / multiplication /
+// addition are correctly rounded on the device as on the host, so the values - and therefore the arg-min (first index of the minimum, as
+// numpy.argmin) - are bit-identical to the host path's.  One workgroup; T <= a few hundred.
+__device__ __forceinline__ double quality_of(const int *__restrict__ c, int j_only) {
+    const double j = c[1] == 0 ? 0.0 : __ddiv_rn((double)c[0], (double)c[1]);
+    if (j_only) return j;
+    const int n_gt = c[2], n_fg = c[3];
+    double p, r;
+    if (n_fg == 0 && n_gt > 0) { p = 1.0; r = 0.0; }
+    else if (n_fg > 0 && n_gt == 0) { p = 0.0; r = 1.0; }
+    else if (n_fg == 0 && n_gt == 0) { p = 1.0; r = 1.0; }
+    else { p = __ddiv_rn((double)c[5], (double)n_fg); r = __ddiv_rn((double)c[4], (double)n_gt); }
+    const double s = __dadd_rn(p, r);
+    const double f = s == 0.0 ? 0.0 : __ddiv_rn(__dmul_rn(__dmul_rn(2.0, p), r), s);
+    return __dmul_rn(0.5, __dadd_rn(j, f));
+}
+
+// first index of the minimum over the workgroup's 256 (best, besti) pairs, each the first minimum of its thread's ascending subsequence
+__device__ __forceinline__ void block_argmin(double best, int besti, int *__restrict__ select) {
+    __shared__ double sv[256];
+    __shared__ int si[256];
+    sv[threadIdx.x] = best; si[threadIdx.x] = besti;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            const double v = sv[threadIdx.x + o]; const int i2 = si[threadIdx.x + o];
+            if (v < sv[threadIdx.x] || (v == sv[threadIdx.x] && i2 < si[threadIdx.x])) { sv[threadIdx.x] = v; si[threadIdx.x] = i2; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) select[0] = si[0];
+}
+
+// object_quality[o][t] = quality_of the counts of object o in frame t, NO_OBJECT where the object is not in the frame's ground truth;
+// quality[t] = the mean over the objects that are - added in ascending o, correctly rounded, then one division by their number - or
+// NO_OBJECT when there is none; select = first index of the minimum of quality (block_argmin).  The host restatement is
+// metrics.label_round_quality.  flags [k][T]: object o is in frame t iff (flags[o][t] != 0) != absent - the label form passes `present`,
+// the binary form k = 1, its `noobj` flags with absent = 1, and no object_quality.  With one object the mean is the object's quality to
+// the bit: quality_of returns non-negative values (quotients, sums and products of non-negative numbers, never -0.0), for which
+// 0.0 + q and q / 1.0 are exact.  One workgroup; T <= a few hundred.
+__global__ __launch_bounds__(256) void round_quality_kernel(const int *__restrict__ counts, const uint8_t *__restrict__ flags, int absent, int k, int T,
+                                                            int j_only, double no_object, double *__restrict__ object_quality,
+                                                            double *__restrict__ quality, int *__restrict__ select) {
+    double best = __builtin_inf();
+    int besti = 0x7fffffff;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        double sum = 0.0;
+        int cnt = 0;
+        for (int o = 0; o < k; ++o) {
+            double q = no_object;
+            if ((flags[o * T + t] != 0) != (absent != 0)) {
+                q = quality_of(counts + ((long)o * T + t) * 6, j_only);
+                sum = __dadd_rn(sum, q);
+                ++cnt;
+            }
+            if (object_quality) object_quality[o * T + t] = q;
+        }
+        const double q = cnt ? __ddiv_rn(sum, (double)cnt) : no_object;
+        quality[t] = q;
+        if (q < best) { best = q; besti = t; }                               // ascending t per thread: the first minimum of its subsequence
+    }
+    block_argmin(best, besti, select);
+}
+
+// One round, three enqueues.  masks / gt / annotated / gen / scratch / counts point at the FIRST of the Tn frames to (re)compose and count,
+// frame t0 of the clip; the quality and the arg-min cover all T_all frames, whose counts start t0 frames earlier: the caller passes the
+// counts of frame t0, and flags, object_quality and quality as whole-clip arrays.  k = 0: binary masks (flags = noobj [T_all], scratch =
+// the boundary map, no object_quality); k >= 1: label maps of k objects (flags = present [k][T_all], scratch = the object sets, counts
+// [k][T_all][6]).
+void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *flags, int k,
+                        int Tn, int H, int W, int radius, double no_object, uint8_t *gen, void *scratch, int *counts, int T_all,
+                        double *object_quality, double *quality, int *select, hipStream_t s, int t0) {
     const long n = (long)Tn * H * W;
     const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(label_compose_kernel, dim3(blocks), dim3(256), 0, s, masks, nh, nw, lh, lw, gt, annotated, k, Tn, H, W, gen);
-    label_counts_launch(gt, gen, k, Tn, H, W, radius, bsets, counts, T_all, s);
-    hipLaunchKernelGGL(label_quality_kernel, dim3(1), dim3(256), 0, s, counts - (long)t0 * 6, present, k, T_all, radius < 0 ? 1 : 0, no_object,
-                       object_quality, quality, select);
+    hipLaunchKernelGGL(k ? round_compose_kernel<true> : round_compose_kernel<false>, dim3(blocks), dim3(256), 0, s, masks, nh, nw, lh, lw, gt, annotated, k,
+                       Tn, H, W, gen);
+    if (k) label_counts_launch(gt, gen, k, Tn, H, W, radius, scratch, counts, T_all, s);
+    else jf_counts_launch(gt, gen, Tn, H, W, radius, (uint8_t *)scratch, counts, s);
+    hipLaunchKernelGGL(round_quality_kernel, dim3(1), dim3(256), 0, s, counts - (long)t0 * 6, flags, k ? 0 : 1, k ? k : 1, T_all, radius < 0 ? 1 : 0,
+                       no_object, k ? object_quality : nullptr, quality, select);
 }
 
 }  // namespace stcn

@@ -29,41 +29,17 @@ import csv
 import os
 import random
 import time
-from typing import List
 
 import numpy as np
 import torch
 
 from . import metrics, shard
-from .fq_driver import NO_OBJECT, ClipDataset, lane_engine_options, run_lanes
+from .fq_driver import NO_OBJECT, ClipDataset, annotation_session, frame_quality, lane_engine_options, run_lanes
 
 POLICIES = ("oracle_mask", "rand_mask", "qnet_mask", "upper_bound_mask")
 MULTI_OBJECT_POLICIES = ("oracle_mask", "rand_mask")          # QNet takes one binary mask; the upper bound builds on the one-object scorer
 MAX_OBJECTS = 32                                              # STCN_MAX_OBJECTS
 MASK_SECONDS, SKIP_SECONDS = 80, 3            # annotation cost model of interactions/mask.py:33-36
-
-
-def frame_quality(processor, gt_thw: torch.Tensor, interacted: List[int], metric: str = "j_and_f"):
-    """``eval_processor_metric`` (interactions/eval.py:27-81) for mask annotations: per-frame J or J&F of the engine's
-    masks against the ground truth, annotated frames counting with their GT mask, NO_OBJECT token for empty GT.
-    Returns (mean over frames with an object, generated masks uint8 [T,H,W] on the device, quality[T])."""
-    lw, uw, lh, uh = processor.pad
-    seg = processor.masks[:, 0, lh:processor.nh - uh, lw:processor.nw - uw] > 0
-    gtb = gt_thw > 0.5
-    gen = seg.clone()
-    if interacted:
-        gen[interacted] = gtb[interacted]
-    rows = metrics.sequence_scores_gpu(gtb, gen, j_only=metric == "j")      # the boundary measure only when it is asked for
-    q = rows[:, 0 if metric == "j" else 2].copy()
-    empty = (gtb.flatten(1).sum(1) == 0).cpu().numpy()
-    mu = float(np.mean(q[~empty])) if (~empty).any() else float("nan")
-    q[empty] = NO_OBJECT
-    return mu, gen.to(torch.uint8), q
-
-
-def _exhausted(q, frames, T):
-    """not_avail_frames (interactions/eval.py:84-89): nothing left to annotate."""
-    return not (set(range(T)) - set(np.where(q == NO_OBJECT)[0].tolist()) - set(frames))
 
 
 def _upper_bound_frame(processor, gt, gt_thw, frames, metric):
@@ -82,84 +58,63 @@ def _upper_bound_frame(processor, gt, gt_thw, frames, metric):
     return best_f
 
 
-def _run_policy_multi_object(policy: str, processor, sample, rounds: int, metric: str, rng):
-    """One VIDEO with all its k objects through ``rounds`` annotation rounds in one engine (``InferenceCore(..., num_objects=k)``): the
-    annotation of frame f is the (k+1)-channel one-hot of its label map, background first, through the reference's ``scribble=True`` path;
-    a round is scored by the k-object evaluation on the device.  The oracle policy takes the arg-min of the FRAME quality (the mean over
-    the objects present in the frame); a frame is valid while any object is present in it."""
-    T, k = sample["num_frames"], int(sample["num_objects"])
-    dev = processor.prob.device
-    scorer = metrics.RoundScorer(sample["gt"][0, :, 0].to(dev), "j" if metric == "j" else "j_and_f", max_rounds=max(rounds, 1),
-                                 no_object=NO_OBJECT, num_objects=k)
-    empty = scorer.empty_host
-    valid = set(np.where(~empty)[0].tolist())
-    channels = torch.arange(k + 1, device=dev, dtype=torch.uint8)[:, None, None, None]
-    frames, times, scored, propagated = [0], [MASK_SECONDS], 0, 0
-    for r in range(1, rounds + 1):
-        if r >= T or (scored and not (valid - set(frames))):       # not_avail_frames, with "frame without any object"
-            continue
-        f = frames[r - 1]
-        processor.interact((scorer.gt[f][None, None] == channels).float(), f, scribble=True, download=False)      # [k+1,1,H,W]
-        propagated += processor.stats()["frames"]
-        worst, _ = scorer.score(processor, frames, keep_gen=False)
-        scored += 1
-        sel = worst if policy == "oracle_mask" else rng.choice(sorted(set(range(T)) - set(frames)))
-        times.append(SKIP_SECONDS if empty[sel] else MASK_SECONDS)
-        frames.append(sel)
-    q, oq = scorer.qualities(), scorer.object_qualities()
-    per_round = [q[i].copy() for i in range(scored)]
-    mus = [float(np.mean(row[~empty])) if (~empty).any() else float("nan") for row in per_round]
-    return dict(mu_metrics=mus, annotation_times=times[:-1], frames=frames, round_metrics=per_round, propagated_frames=propagated,
-                object_metrics=[oq[i].copy() for i in range(scored)], present=scorer.present_host)
-
-
 def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and_f", qnet=None, rng=None, multi_object: bool = False):
     """One sample through ``rounds`` annotation rounds.  Returns dict(mu_metrics, annotation_times, frames,
-    round_metrics): mu_metrics[r] / annotation_times[r] as the reference returns them; frames = annotated frames in
-    order; round_metrics[r] = per-frame quality after round r.
-    ``multi_object``: the sample is a per-video one (``ClipDataset(..., per_video=True)``), the processor holds all its objects; the
-    values above are those of the FRAME quality, and ``object_metrics[r]`` [k,T] / ``present`` [k,T] are added."""
+    round_metrics, propagated_frames): mu_metrics[r] / annotation_times[r] as the reference returns them; frames = annotated frames in
+    order; round_metrics[r] = per-frame quality after round r; propagated_frames = frames the engine really visited (rounds >= 2 only
+    walk the spans next to the new annotation).
+    ``multi_object``: the sample is a per-video one (``ClipDataset(..., per_video=True)``) and the processor holds all its k objects
+    (``InferenceCore(..., num_objects=k)``): the annotation of frame f is the (k+1)-channel one-hot of its label map, background first, through
+    the reference's ``scribble=True`` path; a round is scored by the k-object evaluation on the device, the values above are those of the FRAME
+    quality (the mean over the objects present in the frame; a frame is valid while any object is present in it), and ``object_metrics[r]``
+    [k,T] / ``present`` [k,T] are added."""
     assert policy in POLICIES, policy
-    if multi_object:
-        if policy not in MULTI_OBJECT_POLICIES:
-            raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
-        return _run_policy_multi_object(policy, processor, sample, rounds, metric, rng or random)
+    if multi_object and policy not in MULTI_OBJECT_POLICIES:
+        raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
     T = sample["num_frames"]
     dev = processor.prob.device
-    gt = sample["gt"][0].to(dev)                                   # [T,1,H,W]
-    gt_thw = gt[:, 0]
-    images = sample["rgb"][0].to(dev) if policy == "qnet_mask" else None
     rng = rng or random
     # the evaluation of a round stays on the device (metrics.RoundScorer): one int per round crosses PCIe for the oracle policy, the
     # per-frame quality rows of the whole session are fetched once at the end
-    scorer = metrics.RoundScorer(gt_thw, "j" if metric == "j" else "j_and_f", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
-    empty = scorer.empty_host
-    valid = set(np.where(~empty)[0].tolist())
-    frames, times, scored = [0], [MASK_SECONDS], 0
-    propagated = 0                                                 # frames the engine really visited (rounds >= 2 only walk the spans next to the new annotation)
-    for r in range(1, rounds + 1):
-        if r >= T or (scored and not (valid - set(frames))):       # not_avail_frames (interactions/eval.py:84-89)
-            continue
-        f = frames[r - 1]
-        processor.interact(gt[f][None], f, download=False)
-        propagated += processor.stats()["frames"]
-        worst, gen = scorer.score(processor, frames, keep_gen=policy == "qnet_mask")
-        scored += 1
+    scorer_args = dict(max_rounds=max(rounds, 1), no_object=NO_OBJECT)
+    if multi_object:
+        k = int(sample["num_objects"])
+        scorer = metrics.RoundScorer(sample["gt"][0, :, 0].to(dev), "j" if metric == "j" else "j_and_f", num_objects=k, **scorer_args)
+        channels = torch.arange(k + 1, device=dev, dtype=torch.uint8)[:, None, None, None]
+
+        def annotate(f):
+            processor.interact((scorer.gt[f][None, None] == channels).float(), f, scribble=True, download=False)      # [k+1,1,H,W]
+    else:
+        gt = sample["gt"][0].to(dev)                               # [T,1,H,W]
+        gt_thw = gt[:, 0]
+        images = sample["rgb"][0].to(dev) if policy == "qnet_mask" else None
+        scorer = metrics.RoundScorer(gt_thw, "j" if metric == "j" else "j_and_f", **scorer_args)
+
+        def annotate(f):
+            processor.interact(gt[f][None], f, download=False)
+
+    def choose(worst, gen, frames):
         if policy == "oracle_mask":
-            sel = worst
-        elif policy == "rand_mask":
-            sel = rng.choice(sorted(set(range(T)) - set(frames)))
-        elif policy == "qnet_mask":
+            return worst
+        if policy == "rand_mask":
+            return rng.choice(sorted(set(range(T)) - set(frames)))
+        if policy == "qnet_mask":
             from .qnet import qnet_frame_selection
-            sel = qnet_frame_selection(qnet, images, gen.float(), frames)
-        else:
-            sel = _upper_bound_frame(processor, gt, gt_thw, frames, metric)
-        times.append(SKIP_SECONDS if empty[sel] else MASK_SECONDS)
-        frames.append(sel)
+            return qnet_frame_selection(qnet, images, gen.float(), frames)
+        return _upper_bound_frame(processor, gt, gt_thw, frames, metric)
+
+    stats = {}
+    frames, gens = annotation_session(processor, scorer, T, rounds, annotate, choose, keep_gen=policy == "qnet_mask", stats=stats)
+    empty, scored = scorer.empty_host, len(gens)
+    times = [MASK_SECONDS] + [SKIP_SECONDS if empty[f] else MASK_SECONDS for f in frames[1:]]
     q = scorer.qualities()
     per_round = [q[i].copy() for i in range(scored)]
     mus = [float(np.mean(row[~empty])) if (~empty).any() else float("nan") for row in per_round]
-    return dict(mu_metrics=mus, annotation_times=times[:-1], frames=frames, round_metrics=per_round, propagated_frames=propagated)
+    res = dict(mu_metrics=mus, annotation_times=times[:-1], frames=frames, round_metrics=per_round, propagated_frames=stats.get("propagated_frames", 0))
+    if multi_object:
+        oq = scorer.object_qualities()
+        res.update(object_metrics=[oq[i].copy() for i in range(scored)], present=scorer.present_host)
+    return res
 
 
 def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "oracle_mask", rounds: int = 60,

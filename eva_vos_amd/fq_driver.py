@@ -361,48 +361,67 @@ def make_synthetic_tree(root: str, videos: Dict[str, tuple], seed: int = 0) -> s
 
 
 # ------------------------------------------------------------------------------------------------ policy
-def per_frame_j(processor, gt_dev: torch.Tensor, interacted: List[int]) -> tuple:
-    """J per frame on the GPU.  Annotated frames count with their GT mask (interactions/eval.py:57-60);
-    frames without the object get the NO_OBJECT token.  Returns (quality[T], generated masks uint8 [T,H,W])."""
+def frame_quality(processor, gt_thw: torch.Tensor, interacted: List[int], metric: str = "j_and_f"):
+    """``eval_processor_metric`` (interactions/eval.py:27-81) for mask annotations: per-frame J or J&F of the engine's
+    masks against the ground truth, annotated frames counting with their GT mask (:57-60), NO_OBJECT token for empty GT.
+    Returns (mean over frames with an object, generated masks uint8 [T,H,W] on the device, quality[T])."""
     lw, uw, lh, uh = processor.pad
     seg = processor.masks[:, 0, lh:processor.nh - uh, lw:processor.nw - uw] > 0
-    gtb = gt_dev > 0.5
+    gtb = gt_thw > 0.5
     gen = seg.clone()
     if interacted:
         gen[interacted] = gtb[interacted]
-    rows = metrics.sequence_scores_gpu(gtb, gen, j_only=True)               # the FQ policy selects by J (interactions/mask.py:113-146)
-    q = rows[:, 0].copy()
-    q[(gtb.flatten(1).sum(1) == 0).cpu().numpy()] = NO_OBJECT
-    return q, gen.to(torch.uint8)
+    rows = metrics.sequence_scores_gpu(gtb, gen, j_only=metric == "j")      # the boundary measure only when it is asked for
+    q = rows[:, 0 if metric == "j" else 2].copy()
+    empty = (gtb.flatten(1).sum(1) == 0).cpu().numpy()
+    mu = float(np.mean(q[~empty])) if (~empty).any() else float("nan")
+    q[empty] = NO_OBJECT
+    return mu, gen.to(torch.uint8), q
 
 
-def oracle_rounds(processor, sample, rounds: int = 8, stats: dict = None):
-    """The oracle annotation policy of the FQ dataset (interactions/mask.py:113-156).  `stats` (optional dict, one per caller thread):
-    the frames the engine really visited (`propagated_frames`) and the `interactions` are added to it.
-    Round 6: the evaluation of a round stays on the device (metrics.RoundScorer: compose + J counts + fp64 quality + arg-min in one enqueue);
-    one int per round crosses PCIe, the per-frame J rows of all rounds are fetched once at the end.  Same values, same selection as
-    per_frame_j + numpy.argmin (tests/test_gpu_driver_golden.py)."""
-    T = sample["num_frames"]
-    gt = sample["gt"][0].to(processor.prob.device)              # [T,1,H,W]
-    scorer = metrics.RoundScorer(gt[:, 0], "j", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
-    valid = set(np.where(~scorer.empty_host)[0].tolist())       # frames that can be annotated at all (the others carry the NO_OBJECT token)
-    frames, sels, gens = [0], [], []
+def per_frame_j(processor, gt_dev: torch.Tensor, interacted: List[int]) -> tuple:
+    """J per frame on the GPU - the FQ policy selects by J (interactions/mask.py:113-146).  Returns (quality[T], generated masks uint8 [T,H,W])."""
+    _, gen, q = frame_quality(processor, gt_dev, interacted, "j")
+    return q, gen
+
+
+def annotation_session(processor, scorer, T: int, rounds: int, annotate, choose, keep_gen: bool = True, stats: dict = None):
+    """The annotation-session loop of every mask policy (interactions/mask.py:10-39,113-156): round r annotates frame ``frames[r - 1]``
+    (the first one frame 0), propagates, scores the round on the device (``scorer``: a metrics.RoundScorer) and appends the frame to
+    annotate next.  ``annotate(f)`` hands the annotation of frame f to ``processor.interact``; ``choose(worst, gen, frames)`` is the policy:
+    the next frame, given the scorer's arg-min, the evaluated masks and the frames annotated so far.  A round is skipped when the clip has no
+    more frames than rounds (``r >= T``) or, after the first scored round, when nothing is left to annotate (not_avail_frames,
+    interactions/eval.py:84-89: every frame is annotated or carries the NO_OBJECT token).  ``stats`` (optional dict): the frames the engine
+    really visited (``propagated_frames``) and the ``interactions`` are added to it.  Returns (frames, gens): every frame chosen, frame 0
+    first - one more than the rounds scored -, and the evaluated masks of every scored round (distinct tensors only with ``keep_gen``)."""
+    valid = set(np.where(~scorer.empty_host)[0].tolist())       # frames that can be annotated at all
+    frames, gens = [0], []
     for r in range(1, rounds + 1):
-        if r >= T:
+        if r >= T or (gens and not (valid - set(frames))):
             continue
-        if sels and not (valid - set(frames)):                  # not_avail_frames (interactions/eval.py:84-89): nothing left to annotate
-            continue
-        f = frames[r - 1]
-        processor.interact(gt[f][None], f, download=False)         # [1,1,H,W] mask of the annotated frame
+        annotate(frames[r - 1])
         if stats is not None:
             stats["propagated_frames"] = stats.get("propagated_frames", 0) + processor.stats()["frames"]
             stats["interactions"] = stats.get("interactions", 0) + 1
-        worst, gen = scorer.score(processor, frames[:r])
-        frames.append(worst)
-        sels.append(worst)
+        worst, gen = scorer.score(processor, frames, keep_gen=keep_gen)
         gens.append(gen)
+        frames.append(choose(worst, gen, frames))
+    return frames, gens
+
+
+def oracle_rounds(processor, sample, rounds: int = 8, stats: dict = None):
+    """The oracle annotation policy of the FQ dataset (interactions/mask.py:113-156): annotate the worst frame by J with its ground-truth
+    mask.  `stats` (optional dict, one per caller thread): see annotation_session.
+    Round 6: the evaluation of a round stays on the device (metrics.RoundScorer: compose + J counts + fp64 quality + arg-min in one enqueue);
+    one int per round crosses PCIe, the per-frame J rows of all rounds are fetched once at the end.  Same values, same selection as
+    per_frame_j + numpy.argmin (tests/test_gpu_driver_golden.py).  Returns ([(selected frame, quality[T]) per round], gens)."""
+    gt = sample["gt"][0].to(processor.prob.device)              # [T,1,H,W]
+    scorer = metrics.RoundScorer(gt[:, 0], "j", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
+    frames, gens = annotation_session(processor, scorer, sample["num_frames"], rounds,
+                                      lambda f: processor.interact(gt[f][None], f, download=False),       # [1,1,H,W] mask of the annotated frame
+                                      lambda worst, gen, frames: worst, stats=stats)
     q = scorer.qualities()
-    return [(w, q[i]) for i, w in enumerate(sels)], gens
+    return [(w, q[i]) for i, w in enumerate(frames[1:])], gens
 
 
 # ------------------------------------------------------------------------------------------------ output

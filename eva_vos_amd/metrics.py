@@ -125,43 +125,23 @@ def label_round_quality(gt: np.ndarray, gen: np.ndarray, num_objects: int, metri
     return q, Q, int(np.argmin(Q))
 
 
-def sequence_scores_gpu(gt, pred, j_only: bool = False):
-    """J, F, J&F per frame on the GPU (HIP kernels behind ``stcn_metrics_jf_counts``).
-    gt, pred: torch uint8/bool tensors [T,H,W] on the same cuda device (non-zero = object).
-    Returns float64 [T,3]; only the 6*T integer counts cross PCIe.  ``j_only``: the region measure alone (``stcn_metrics_j_counts``:
-    no boundary maps, no disk matching) - column 0 is J, columns 1 and 2 are NaN."""
-    import ctypes as C
-
-    import torch
-
-    from . import _lib
-    gt = (gt != 0).to(torch.uint8).contiguous()
-    pred = (pred != 0).to(torch.uint8).contiguous()
-    assert gt.is_cuda and pred.is_cuda and gt.shape == pred.shape and gt.dim() == 3
-    T, H, W = gt.shape
-    with torch.cuda.device(gt.device):
-        counts = torch.empty((T, 6), dtype=torch.int32, device=gt.device)
-        if j_only:
-            _lib.check(_lib.lib().stcn_metrics_j_counts(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.c_void_p(gt.data_ptr()),
-                                                        C.c_void_p(pred.data_ptr()), T, H, W, C.c_void_p(counts.data_ptr())), "stcn_metrics_j_counts")
-            c = counts.cpu().numpy()
-            out = np.full((T, 3), np.nan)
-            out[:, 0] = np.where(c[:, 1] > 0, c[:, 0] / np.maximum(c[:, 1], 1), 0.0)
-            return out
-        scratch = torch.empty((T * H * W,), dtype=torch.uint8, device=gt.device)
-        _lib.check(_lib.lib().stcn_metrics_jf_counts(C.c_void_p(torch.cuda.current_stream().cuda_stream),
-                                                     C.c_void_p(gt.data_ptr()), C.c_void_p(pred.data_ptr()), T, H, W,
-                                                     C.c_void_p(counts.data_ptr()), C.c_void_p(scratch.data_ptr())),
-                   "stcn_metrics_jf_counts")
-        c = counts.cpu().numpy()
-    return _scores_from_counts(c)
-
-
 def _check_num_objects(k) -> int:
     k = int(k)
     if not 1 <= k <= 32:
         raise ValueError(f"num_objects = {k}: the library is built for 1..32 objects (STCN_MAX_OBJECTS)")
     return k
+
+
+def _ptr(t):
+    import ctypes as C
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _stream():
+    import ctypes as C
+
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _objects_scratch(k: int, T: int, H: int, W: int, device):
@@ -176,36 +156,50 @@ def _objects_scratch(k: int, T: int, H: int, W: int, device):
     return torch.empty((int(n.value),), dtype=torch.uint8, device=device)
 
 
+def _boundary_scratch(k, T: int, H: int, W: int, device):
+    """A byte per pixel for binary masks (k None), ``_objects_scratch`` for label maps."""
+    import torch
+    return torch.empty((T * H * W,), dtype=torch.uint8, device=device) if k is None else _objects_scratch(k, T, H, W, device)
+
+
+def _scores_gpu(gt, pred, k, j_only: bool):
+    """The counts of the binary masks (k None: ``stcn_metrics_j[f]_counts``) or of the label maps of k objects
+    (``stcn_metrics_objects_j[f]_counts``) gt, pred - uint8 [T,H,W], contiguous, on one cuda device - downloaded (only the integers cross
+    PCIe) and turned into rows (J, F, J&F) per frame, float64 [T,3] or [k,T,3]; ``j_only``: columns 1 and 2 are NaN."""
+    import torch
+
+    from . import _lib
+    assert gt.is_cuda and pred.is_cuda and gt.shape == pred.shape and gt.dim() == 3 and gt.dtype == pred.dtype == torch.uint8
+    T, H, W = gt.shape
+    name = f"stcn_metrics_{'' if k is None else 'objects_'}{'j' if j_only else 'jf'}_counts"
+    with torch.cuda.device(gt.device):
+        counts = torch.empty((T, 6) if k is None else (k, T, 6), dtype=torch.int32, device=gt.device)
+        scratch = () if j_only else (_boundary_scratch(k, T, H, W, gt.device),)
+        _lib.check(getattr(_lib.lib(), name)(_stream(), _ptr(gt), _ptr(pred), *(() if k is None else (k,)), T, H, W, _ptr(counts),
+                                             *map(_ptr, scratch)), name)
+        c = counts.cpu().numpy()
+    if j_only:
+        out = np.full(c.shape[:-1] + (3,), np.nan)
+        out[..., 0] = np.where(c[..., 1] > 0, c[..., 0] / np.maximum(c[..., 1], 1), 0.0)
+        return out
+    return _scores_from_counts(c) if k is None else np.stack([_scores_from_counts(c[o]) for o in range(k)])
+
+
+def sequence_scores_gpu(gt, pred, j_only: bool = False):
+    """J, F, J&F per frame on the GPU (HIP kernels behind ``stcn_metrics_jf_counts``).
+    gt, pred: torch uint8/bool tensors [T,H,W] on the same cuda device (non-zero = object).
+    Returns float64 [T,3]; only the 6*T integer counts cross PCIe.  ``j_only``: the region measure alone (``stcn_metrics_j_counts``:
+    no boundary maps, no disk matching) - column 0 is J, columns 1 and 2 are NaN."""
+    import torch
+    return _scores_gpu((gt != 0).to(torch.uint8).contiguous(), (pred != 0).to(torch.uint8).contiguous(), None, j_only)
+
+
 def sequence_scores_objects_gpu(gt, pred, num_objects: int, j_only: bool = False):
     """``sequence_scores_gpu`` for label maps of ``num_objects`` objects: gt, pred uint8 [T,H,W] on the same cuda device (0 = background,
     o = object o, a label above ``num_objects`` = background).  Returns float64 [k,T,3] - rows (J, F, J&F) of object o + 1 as
     ``sequence_scores_gpu(gt == o + 1, pred == o + 1)`` returns them - from ONE pass over the pixels (``stcn_metrics_objects_jf_counts``;
     ``j_only``: ``stcn_metrics_objects_j_counts``, columns 1 and 2 NaN)."""
-    import ctypes as C
-
-    import torch
-
-    from . import _lib
-    k = _check_num_objects(num_objects)
-    assert gt.is_cuda and pred.is_cuda and gt.shape == pred.shape and gt.dim() == 3 and gt.dtype == pred.dtype == torch.uint8
-    gt, pred = gt.contiguous(), pred.contiguous()
-    T, H, W = gt.shape
-    with torch.cuda.device(gt.device):
-        counts = torch.empty((k, T, 6), dtype=torch.int32, device=gt.device)
-        s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if j_only:
-            _lib.check(_lib.lib().stcn_metrics_objects_j_counts(s, C.c_void_p(gt.data_ptr()), C.c_void_p(pred.data_ptr()), k, T, H, W,
-                                                                C.c_void_p(counts.data_ptr())), "stcn_metrics_objects_j_counts")
-            c = counts.cpu().numpy()
-            out = np.full((k, T, 3), np.nan)
-            out[..., 0] = np.where(c[..., 1] > 0, c[..., 0] / np.maximum(c[..., 1], 1), 0.0)
-            return out
-        scratch = _objects_scratch(k, T, H, W, gt.device)
-        _lib.check(_lib.lib().stcn_metrics_objects_jf_counts(s, C.c_void_p(gt.data_ptr()), C.c_void_p(pred.data_ptr()), k, T, H, W,
-                                                             C.c_void_p(counts.data_ptr()), C.c_void_p(scratch.data_ptr())),
-                   "stcn_metrics_objects_jf_counts")
-        c = counts.cpu().numpy()
-    return np.stack([_scores_from_counts(c[o]) for o in range(k)])
+    return _scores_gpu(gt.contiguous(), pred.contiguous(), _check_num_objects(num_objects), j_only)
 
 
 class RoundScorer:
@@ -225,37 +219,42 @@ class RoundScorer:
 
     def __init__(self, gt_thw, metric: str = "j", max_rounds: int = 64, no_object: float = 20.0, num_objects=None):
         import torch
+
+        from . import _lib
         assert gt_thw.is_cuda and gt_thw.dim() == 3
         self.metric, self.no_object = metric, float(no_object)
         self.dev = gt_thw.device
-        self.k = None if num_objects is None else _check_num_objects(num_objects)
-        if self.k is None:
+        self.T, self.H, self.W = T, H, W = tuple(int(v) for v in gt_thw.shape)
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.dev)      # noqa: E731
+        # binary masks or label maps: decided here, once - the entry point, what it takes between `annotated` and T (``_which``) and
+        # where the per-object rows of round r go (``_object_rows``); score() is the same for both
+        if num_objects is None:
+            self.k, self.object_quality = None, None
             self.gt = (gt_thw > 0.5 if gt_thw.is_floating_point() else gt_thw != 0).to(torch.uint8).contiguous()
+            empty = self.gt.flatten(1).sum(1) == 0
+            self.noobj = empty.to(torch.uint8).contiguous()
+            self.counts = new((T, 6), torch.int32)
+            self._entry, self._which, self._object_rows = "stcn_metrics_round", (_ptr(self.noobj),), lambda r: ()
         else:
+            self.k = _check_num_objects(num_objects)
             assert gt_thw.dtype == torch.uint8, "a label map is uint8"
             self.gt = torch.where(gt_thw > self.k, torch.zeros_like(gt_thw), gt_thw).contiguous()      # objects that appear later: background
-        self.T, self.H, self.W = (int(v) for v in self.gt.shape)
-        if self.k is not None:
             present = torch.stack([(self.gt == o).flatten(1).any(1) for o in range(1, self.k + 1)])     # [k,T], once per sample
             self.present = present.to(torch.uint8).contiguous()
             self.present_host = present.cpu().numpy()                 # ONE sync per sample
             empty = ~present.any(0)                                   # frames without any object carry the NO_OBJECT token
-            self.object_quality = torch.empty((max_rounds, self.k, self.T), dtype=torch.float64, device=self.dev)
-        else:
-            empty = self.gt.flatten(1).sum(1) == 0
-        self.noobj = empty.to(torch.uint8).contiguous()
+            self.noobj = empty.to(torch.uint8).contiguous()
+            self.object_quality = new((max_rounds, self.k, T), torch.float64)
+            self.counts = new((self.k, T, 6), torch.int32)
+            self._entry, self._which = "stcn_metrics_objects_round", (_ptr(self.present), self.k)
+            self._object_rows = lambda r: (_ptr(self.object_quality[r]),)
+        self._enqueue = getattr(_lib.lib(), self._entry)
         self.empty_host = empty.cpu().numpy()                         # ONE sync per sample: which frames carry the NO_OBJECT token
-        self.annotated = torch.zeros(self.T, dtype=torch.uint8, device=self.dev)
-        self.flags_host = torch.zeros(self.T, dtype=torch.uint8).pin_memory()
-        self.counts = torch.empty((self.T, 6) if self.k is None else (self.k, self.T, 6), dtype=torch.int32, device=self.dev)
-        if metric == "j":
-            self.scratch = None
-        elif self.k is None:
-            self.scratch = torch.empty((self.T * self.H * self.W,), dtype=torch.uint8, device=self.dev)
-        else:
-            self.scratch = _objects_scratch(self.k, self.T, self.H, self.W, self.dev)
-        self.quality = torch.empty((max_rounds, self.T), dtype=torch.float64, device=self.dev)
-        self.select = torch.empty((max_rounds,), dtype=torch.int32, device=self.dev)
+        self.annotated = torch.zeros(T, dtype=torch.uint8, device=self.dev)
+        self.flags_host = torch.zeros(T, dtype=torch.uint8).pin_memory()
+        self.scratch = None if metric == "j" else _boundary_scratch(self.k, T, H, W, self.dev)
+        self.quality = new((max_rounds, T), torch.float64)
+        self.select = new((max_rounds,), torch.int32)
         self.select_host = torch.empty((max_rounds,), dtype=torch.int32).pin_memory()
         self.event = torch.cuda.Event(blocking=True)
         self.rounds = 0
@@ -266,8 +265,6 @@ class RoundScorer:
         every frame annotated so far, the one annotated in THIS round last.  ``incremental``: from the second round on only the frames the
         round can have changed - between the neighbouring annotated frames of the new one - are composed and counted again (the masks of the
         others are what they were: the engine only rewrites the probabilities of the frames it visits)."""
-        import ctypes as C
-
         import torch
 
         from . import _lib
@@ -294,18 +291,10 @@ class RoundScorer:
             else:
                 gen = prev
             self._gen = gen
-            p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
-            if self.k is None:
-                _lib.check(_lib.lib().stcn_metrics_round(
-                    C.c_void_p(torch.cuda.current_stream().cuda_stream), p(processor.masks), processor.nh, processor.nw, lh, lw, p(self.gt),
-                    p(self.annotated), p(self.noobj), self.T, self.H, self.W, t0, t1, 1 if self.metric == "j" else 0, self.no_object, p(gen),
-                    p(self.scratch), p(self.counts), p(self.quality[r]), p(self.select[r:r + 1])), "stcn_metrics_round")
-            else:
-                _lib.check(_lib.lib().stcn_metrics_objects_round(
-                    C.c_void_p(torch.cuda.current_stream().cuda_stream), p(processor.masks), processor.nh, processor.nw, lh, lw, p(self.gt),
-                    p(self.annotated), p(self.present), self.k, self.T, self.H, self.W, t0, t1, 1 if self.metric == "j" else 0, self.no_object,
-                    p(gen), p(self.scratch), p(self.counts), p(self.object_quality[r]), p(self.quality[r]), p(self.select[r:r + 1])),
-                    "stcn_metrics_objects_round")
+            _lib.check(self._enqueue(
+                _stream(), _ptr(processor.masks), processor.nh, processor.nw, lh, lw, _ptr(self.gt), _ptr(self.annotated), *self._which,
+                self.T, self.H, self.W, t0, t1, 1 if self.metric == "j" else 0, self.no_object, _ptr(gen), _ptr(self.scratch), _ptr(self.counts),
+                *self._object_rows(r), _ptr(self.quality[r]), _ptr(self.select[r:r + 1])), self._entry)
             self.select_host[r:r + 1].copy_(self.select[r:r + 1], non_blocking=True)
             self.event.record()
             self.event.synchronize()                                  # blocking wait: the lane's host thread sleeps until the round is done
@@ -318,6 +307,6 @@ class RoundScorer:
 
     def object_qualities(self):
         """float64 [rounds, k, T]: the per-object quality of every round of a multi-object session scored so far (one D2H copy)."""
-        if self.k is None:
+        if self.object_quality is None:
             raise RuntimeError("RoundScorer.object_qualities: a one-object scorer (num_objects=None) has the rows of qualities() only")
         return self.object_quality[: self.rounds].cpu().numpy()

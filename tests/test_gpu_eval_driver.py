@@ -134,3 +134,58 @@ def test_round_scorer_on_the_device_equals_the_host_path_bit_for_bit(metric, H, 
         assert torch.equal(gen, gen_ref), r
         assert all(q[f] == (eval_driver.NO_OBJECT if f in (3, 9) else 1.0) for f in annotated)
     assert sc.qualities().shape == (5, T)
+
+
+@pytest.mark.parametrize("metric", ["j", "j_and_f"])
+def test_incremental_binary_rounds_equal_numpy_and_scipy(metric):
+    """An anchor that shares nothing with the kernels: three incremental rounds of metrics.RoundScorer against the host measures
+    (metrics.jaccard / metrics.f_measure, what metrics.sequence_scores computes per frame: NumPy + SciPy), the NO_OBJECT token and
+    numpy.argmin - counts equal, quality equal as float64 bit patterns, selection equal.  T = 5 frames of 37 x 53: radius 1, and 1961
+    pixels per frame against 1024 per wave, so most waves lie across a frame boundary; the engine tensor is padded to 48 x 64 with garbage
+    in the padding; frame 3 has no object.  Before rounds 2 and 3 the masks inside the round's window are flipped at ~1 %; round 3
+    (annotating frame 2 between 0 and 4) recounts frames 1..3 only."""
+    from eva_vos_amd import metrics
+
+    class Proc:
+        pass
+    T, H, W, NO = 5, 37, 53, eval_driver.NO_OBJECT
+    rng = np.random.RandomState(7)
+    gt = synth.synthetic_mask(T, H, W, 1, seed=5)[0, :, 0] > 0.5
+    gt[3] = False
+    pred = (synth.synthetic_mask(T, H, W, 1, seed=6)[0, :, 0] > 0.5) ^ torch.from_numpy(rng.rand(T, H, W) < 0.02)
+    p = Proc()
+    p.nh, p.nw, lh, lw = 48, 64, 5, 5
+    p.pad = (lw, p.nw - W - lw, lh, p.nh - H - lh)
+    masks = torch.from_numpy(rng.randint(0, 256, (T, 1, p.nh, p.nw)).astype(np.uint8))      # garbage in the padding
+    masks[:, 0, lh:lh + H, lw:lw + W] = pred.to(torch.uint8)
+    p.masks = masks.cuda()
+    gt_h = gt.numpy()
+    sc = metrics.RoundScorer(gt.cuda(), metric, max_rounds=3, no_object=NO)
+    quality = []
+    for r, (annotated, window) in enumerate((([0], (0, T)), ([0, 4], (1, T)), ([0, 4, 2], (1, 4)))):
+        if r:
+            flip = torch.from_numpy(rng.rand(window[1] - window[0], H, W) < 0.01).to(torch.uint8).cuda()
+            p.masks[window[0]:window[1], 0, lh:lh + H, lw:lw + W] ^= flip
+        sel, gen = sc.score(p, annotated)
+        gen_h = p.masks[:, 0, lh:lh + H, lw:lw + W].cpu().numpy() != 0
+        gen_h[annotated] = gt_h[annotated]
+        assert np.array_equal(gen.cpu().numpy(), gen_h.astype(np.uint8)), r
+        counts = metrics.label_counts(gt_h, gen_h, 1)[0]                              # NumPy / SciPy, [T,6]
+        got = sc.counts.cpu().numpy()
+        print(r, metric, "counts", got.tolist(), "host", counts.tolist())
+        if metric == "j":
+            assert np.array_equal(got[:, :2], counts[:, :2]) and not got[:, 2:].any(), r
+        else:
+            assert np.array_equal(got, counts), r
+        jf = np.array([(metrics.jaccard(gt_h[t], gen_h[t]), metrics.f_measure(gt_h[t], gen_h[t])) for t in range(T)], np.float64)
+        rows = metrics.sequence_scores(gt_h, gen_h)                                  # float32 rows (frame, J, F, J&F) of the same values
+        assert np.array_equal(rows[:, 1:3], jf.astype(np.float32))
+        q_ref = jf[:, 0].copy() if metric == "j" else 0.5 * (jf[:, 0] + jf[:, 1])
+        q_ref[3] = NO
+        q = sc.qualities()[r]
+        print(r, metric, "quality", q.tolist(), "host", q_ref.tolist(), "selected", sel)
+        assert q.dtype == np.float64 and np.array_equal(q.view(np.uint64), q_ref.view(np.uint64)), (r, q, q_ref)
+        assert sel == int(np.argmin(q_ref)), (r, sel)
+        quality.append(q)
+    assert (quality[2][[1, 2, 3]] != quality[1][[1, 2, 3]]).any(), "round 3 changed nothing inside its window"
+    assert np.array_equal(quality[2][[0, 4]], quality[1][[0, 4]])

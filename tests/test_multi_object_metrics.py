@@ -56,6 +56,31 @@ def test_bad_arguments_are_refused_with_a_message_before_any_device_call():
     _refused(lib.stcn_metrics_objects_round(None, P, 40, 64, 4, 2, P, P, P, 3, 4, 40, 60, 0, 4, 0, 20.0, P, P, P, P, P, P), "crop")
 
 
+def test_the_binary_entry_points_say_what_is_wrong_too():
+    lib = _lib.lib()
+
+    def rnd(t0=0, t1=4, nh=48, H=40, **null):
+        a = dict(masks=P, gt=P, annotated=P, noobj=P, gen=P, scratch=P, counts=P, q=P, select=P)
+        a.update({n: None for n in null})
+        return lib.stcn_metrics_round(None, a["masks"], nh, 64, 4, 2, a["gt"], a["annotated"], a["noobj"], 4, H, 60, t0, t1, 0, 20.0, a["gen"],
+                                      a["scratch"], a["counts"], a["q"], a["select"])
+    _refused(lib.stcn_metrics_jf_counts(None, P, P, 4, 1, 60, P, P), "stcn_metrics_jf_counts", "bad shape", "H, W >= 2", "H=1")
+    _refused(lib.stcn_metrics_j_counts(None, P, P, 4, 40, 0, P), "stcn_metrics_j_counts", "bad shape", "H, W >= 1", "W=0")
+    _refused(lib.stcn_metrics_jf_counts(None, P, P, 0, 40, 60, P, P), "stcn_metrics_jf_counts", "bad shape", "T=0")
+    for hole in range(4):
+        a = [P] * 4
+        a[hole] = None
+        _refused(lib.stcn_metrics_jf_counts(None, a[0], a[1], 4, 40, 60, a[2], a[3]), "stcn_metrics_jf_counts", "null")
+        if hole < 3:
+            _refused(lib.stcn_metrics_j_counts(None, a[0], a[1], 4, 40, 60, a[2]), "stcn_metrics_j_counts", "null")
+    for name in ("masks", "gt", "annotated", "noobj", "gen", "scratch", "counts", "q", "select"):
+        _refused(rnd(**{name: True}), "stcn_metrics_round", "null")
+    _refused(rnd(H=1), "stcn_metrics_round", "bad shape")
+    _refused(rnd(nh=40), "stcn_metrics_round", "crop")
+    for t0, t1 in ((3, 2), (2, 2), (-1, 2), (0, 5)):
+        _refused(rnd(t0=t0, t1=t1), "stcn_metrics_round", f"[{t0}, {t1})")
+
+
 def test_scratch_size_is_stated_by_the_library():
     lib = _lib.lib()
     n = C.c_int64()
