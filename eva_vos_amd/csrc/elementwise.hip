@@ -6,6 +6,9 @@ namespace stcn {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// Blocks of a launch over n work items, `per` per block, at most `cap`: every kernel launched with it walks its items with the stride of the
+// grid (for (i = first; i < n; i += gridDim.x * 256)), so a launch of more than cap * per items (2^28 by default: argmax over 648 frames of
+// 480p) takes further passes of the same grid instead of dropping the rest
 static inline unsigned nblocks(long n, int per = 256, long cap = 1 << 20) {
     long b = (n + per - 1) / per;
     if (b < 1) b = 1;
@@ -19,16 +22,16 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-
 // image NCHW [3,H,W] -> NHWC4 [nh,nw,4] with symmetric zero pad (tensor_util.py:62-80)
 __global__ void pack_image_kernel(const float *__restrict__ img, float *__restrict__ out, int H, int W,
                                   int nh, int nw, int lw, int lh) {
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i >= (long)nh * nw) return;
-    const int y = (int)(i / nw), x = (int)(i - (long)y * nw);
-    const int sy = y - lh, sx = x - lw;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if ((unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W) {
-        const long o = (long)sy * W + sx, pl = (long)H * W;
-        v.x = img[o]; v.y = img[o + pl]; v.z = img[o + 2 * pl];
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < (long)nh * nw; i += (long)gridDim.x * 256) {
+        const int y = (int)(i / nw), x = (int)(i - (long)y * nw);
+        const int sy = y - lh, sx = x - lw;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if ((unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W) {
+            const long o = (long)sy * W + sx, pl = (long)H * W;
+            v.x = img[o]; v.y = img[o + pl]; v.z = img[o + 2 * pl];
+        }
+        *reinterpret_cast<f32x4 *>(out + i * 4) = v;
     }
-    *reinterpret_cast<f32x4 *>(out + i * 4) = v;
 }
 void pack_image_launch(const float *img, float *out, int H, int W, int nh, int nw, int lw, int lh,
                        hipStream_t s) {
@@ -39,18 +42,18 @@ void pack_image_launch(const float *img, float *out, int H, int W, int nh, int n
 // value-encoder input (prop_net.py:157-169, modules.py:119): [k,npix,8] = rgb, mask_i, others_i, 0,0,0
 __global__ void pack_value_input_kernel(const float *__restrict__ img4, const float *__restrict__ masks,
                                         long mstride, int k, int npix, float *__restrict__ out) {
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i >= (long)k * npix) return;
-    const int b = (int)(i / npix), pix = (int)(i - (long)b * npix);
-    const f32x4 im = *reinterpret_cast<const f32x4 *>(img4 + (long)pix * 4);
-    const float me = masks[b * mstride + pix];
-    // others = sum of the other masks (exactly zero for k == 1, as torch.zeros_like)
-    float others = 0.f;
-    for (int j = 0; j < k; ++j)
-        if (j != b) others += masks[j * mstride + pix];
-    f32x4 a = {im.x, im.y, im.z, me}, c = {others, 0.f, 0.f, 0.f};
-    *reinterpret_cast<f32x4 *>(out + i * 8) = a;
-    *reinterpret_cast<f32x4 *>(out + i * 8 + 4) = c;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < (long)k * npix; i += (long)gridDim.x * 256) {
+        const int b = (int)(i / npix), pix = (int)(i - (long)b * npix);
+        const f32x4 im = *reinterpret_cast<const f32x4 *>(img4 + (long)pix * 4);
+        const float me = masks[b * mstride + pix];
+        // others = sum of the other masks (exactly zero for k == 1, as torch.zeros_like)
+        float others = 0.f;
+        for (int j = 0; j < k; ++j)
+            if (j != b) others += masks[j * mstride + pix];
+        f32x4 a = {im.x, im.y, im.z, me}, c = {others, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4 *>(out + i * 8) = a;
+        *reinterpret_cast<f32x4 *>(out + i * 8 + 4) = c;
+    }
 }
 void pack_value_input_launch(const float *img4, const float *masks, long mask_stride, int k, int npix,
                              float *out, hipStream_t s) {
@@ -61,31 +64,31 @@ void pack_value_input_launch(const float *img4, const float *masks, long mask_st
 // MaxPool2d(3, stride 2, pad 1) (modules.py:113,144): -inf padding
 __global__ void maxpool_kernel(const float *__restrict__ x, float *__restrict__ y, int B, int H, int W, int C) {
     const int OH = H / 2, OW = W / 2, C4 = C / 4;
-    const long i = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x) * 256L + threadIdx.x;      // neighbouring output rows share an input row
-    if (i >= (long)B * OH * OW * C4) return;
-    const int c4 = (int)(i % C4);
-    long r = i / C4;
-    const int ow = (int)(r % OW); r /= OW;
-    const int oh = (int)(r % OH);
-    const int b = (int)(r / OH);
-    // taps outside the image are CLAMPED to the edge pixel, which is inside the window anyway - the same maximum without a
-    // branch per tap (a `continue` in front of each load made hipcc wait for every load before issuing the next: 9 serialized
-    // round trips per output).  With even H, W (all the engine passes) only the top / left taps can leave the image; the bottom /
-    // right clamp keeps an odd size inside the buffer (OH = H / 2 rows are produced either way)
-    const int iy0 = max(2 * oh - 1, 0), ix0 = max(2 * ow - 1, 0), iy2 = min(2 * oh + 1, H - 1), ix2 = min(2 * ow + 1, W - 1);
-    const float *xb = x + (long)b * H * W * C + c4 * 4;
-    f32x4 v[9];
+    for (long i = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x) * 256L + threadIdx.x; i < (long)B * OH * OW * C4; i += (long)gridDim.x * 256) {
+        const int c4 = (int)(i % C4);
+        long r = i / C4;
+        const int ow = (int)(r % OW); r /= OW;
+        const int oh = (int)(r % OH);
+        const int b = (int)(r / OH);
+        // taps outside the image are CLAMPED to the edge pixel, which is inside the window anyway - the same maximum without a
+        // branch per tap (a `continue` in front of each load made hipcc wait for every load before issuing the next: 9 serialized
+        // round trips per output).  With even H, W (all the engine passes) only the top / left taps can leave the image; the bottom /
+        // right clamp keeps an odd size inside the buffer (OH = H / 2 rows are produced either way)
+        const int iy0 = max(2 * oh - 1, 0), ix0 = max(2 * ow - 1, 0), iy2 = min(2 * oh + 1, H - 1), ix2 = min(2 * ow + 1, W - 1);
+        const float *xb = x + (long)b * H * W * C + c4 * 4;
+        f32x4 v[9];
 #pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
+        for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const int iy = dy == 0 ? iy0 : (dy == 2 ? iy2 : 2 * oh), ix = dx == 0 ? ix0 : (dx == 2 ? ix2 : 2 * ow);
-            v[dy * 3 + dx] = *reinterpret_cast<const f32x4 *>(xb + ((long)iy * W + ix) * C);
-        }
-    f32x4 m = v[0];
+            for (int dx = 0; dx < 3; ++dx) {
+                const int iy = dy == 0 ? iy0 : (dy == 2 ? iy2 : 2 * oh), ix = dx == 0 ? ix0 : (dx == 2 ? ix2 : 2 * ow);
+                v[dy * 3 + dx] = *reinterpret_cast<const f32x4 *>(xb + ((long)iy * W + ix) * C);
+            }
+        f32x4 m = v[0];
 #pragma unroll
-    for (int t = 1; t < 9; ++t) { m.x = fmaxf(m.x, v[t].x); m.y = fmaxf(m.y, v[t].y); m.z = fmaxf(m.z, v[t].z); m.w = fmaxf(m.w, v[t].w); }
-    *reinterpret_cast<f32x4 *>(y + i * 4) = m;
+        for (int t = 1; t < 9; ++t) { m.x = fmaxf(m.x, v[t].x); m.y = fmaxf(m.y, v[t].y); m.z = fmaxf(m.z, v[t].z); m.w = fmaxf(m.w, v[t].w); }
+        *reinterpret_cast<f32x4 *>(y + i * 4) = m;
+    }
 }
 // test aid: keeps a stream busy for `us` microseconds (wall_clock64: the constant 100 MHz counter)
 __global__ void spin_kernel(long ticks) {
@@ -115,29 +118,29 @@ __global__ void upsample2x_add_kernel(const float *__restrict__ x, const float *
     const int OH = 2 * h, OW = 2 * w, C4 = C / 4;
     // XCD-contiguous: an output row pair shares its two low-resolution source rows; dealt round-robin every XCD pulled (nearly) all of x
     // into its own L2 (385 MB fetched for 300 algorithmic at 1/4 scale over a 5-frame group)
-    const long i = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x) * 256L + threadIdx.x;
-    if (i >= (long)B * OH * OW * C4) return;
-    const int c4 = (int)(i % C4);
-    long r = i / C4;
-    const int ox = (int)(r % OW); r /= OW;
-    const int oy = (int)(r % OH);
-    const int b = (int)(r / OH);
-    int y0, y1, x0, x1; float fy, fx;
-    bil(oy, 0.5f, h, y0, y1, fy);
-    bil(ox, 0.5f, w, x0, x1, fx);
-    const float *xb = x + (long)b * h * w * C + c4 * 4;
-    const f32x4 v00 = *reinterpret_cast<const f32x4 *>(xb + ((long)y0 * w + x0) * C);
-    const f32x4 v01 = *reinterpret_cast<const f32x4 *>(xb + ((long)y0 * w + x1) * C);
-    const f32x4 v10 = *reinterpret_cast<const f32x4 *>(xb + ((long)y1 * w + x0) * C);
-    const f32x4 v11 = *reinterpret_cast<const f32x4 *>(xb + ((long)y1 * w + x1) * C);
-    const f32x4 sk = *reinterpret_cast<const f32x4 *>(skip + (long)(skip_bmod ? b % skip_bmod : b) * skip_bs + ((long)oy * OW + ox) * C + c4 * 4);
-    const float w00 = (1.f - fy) * (1.f - fx), w01 = (1.f - fy) * fx, w10 = fy * (1.f - fx), w11 = fy * fx;
-    f32x4 o;
-    o.x = sk.x + (w00 * v00.x + w01 * v01.x + w10 * v10.x + w11 * v11.x);
-    o.y = sk.y + (w00 * v00.y + w01 * v01.y + w10 * v10.y + w11 * v11.y);
-    o.z = sk.z + (w00 * v00.z + w01 * v01.z + w10 * v10.z + w11 * v11.z);
-    o.w = sk.w + (w00 * v00.w + w01 * v01.w + w10 * v10.w + w11 * v11.w);
-    *reinterpret_cast<f32x4 *>(u + i * 4) = o;
+    for (long i = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x) * 256L + threadIdx.x; i < (long)B * OH * OW * C4; i += (long)gridDim.x * 256) {
+        const int c4 = (int)(i % C4);
+        long r = i / C4;
+        const int ox = (int)(r % OW); r /= OW;
+        const int oy = (int)(r % OH);
+        const int b = (int)(r / OH);
+        int y0, y1, x0, x1; float fy, fx;
+        bil(oy, 0.5f, h, y0, y1, fy);
+        bil(ox, 0.5f, w, x0, x1, fx);
+        const float *xb = x + (long)b * h * w * C + c4 * 4;
+        const f32x4 v00 = *reinterpret_cast<const f32x4 *>(xb + ((long)y0 * w + x0) * C);
+        const f32x4 v01 = *reinterpret_cast<const f32x4 *>(xb + ((long)y0 * w + x1) * C);
+        const f32x4 v10 = *reinterpret_cast<const f32x4 *>(xb + ((long)y1 * w + x0) * C);
+        const f32x4 v11 = *reinterpret_cast<const f32x4 *>(xb + ((long)y1 * w + x1) * C);
+        const f32x4 sk = *reinterpret_cast<const f32x4 *>(skip + (long)(skip_bmod ? b % skip_bmod : b) * skip_bs + ((long)oy * OW + ox) * C + c4 * 4);
+        const float w00 = (1.f - fy) * (1.f - fx), w01 = (1.f - fy) * fx, w10 = fy * (1.f - fx), w11 = fy * fx;
+        f32x4 o;
+        o.x = sk.x + (w00 * v00.x + w01 * v01.x + w10 * v10.x + w11 * v11.x);
+        o.y = sk.y + (w00 * v00.y + w01 * v01.y + w10 * v10.y + w11 * v11.y);
+        o.z = sk.z + (w00 * v00.z + w01 * v01.z + w10 * v10.z + w11 * v11.z);
+        o.w = sk.w + (w00 * v00.w + w01 * v01.w + w10 * v10.w + w11 * v11.w);
+        *reinterpret_cast<f32x4 *>(u + i * 4) = o;
+    }
 }
 void upsample2x_add_launch(const float *x, const float *skip, float *u, int B, int h, int w, int C,
                            hipStream_t s, long skip_bs, int skip_bmod) {
@@ -184,32 +187,32 @@ template <int MAXOBJ, bool AGG = true>
 __global__ void up4_sigmoid_aggregate_kernel(const float *__restrict__ logit4, int k, int h4, int w4,
                                              float *__restrict__ agg, long stride, long obj_stride, long logit_gs, long agg_gs) {
     const int H = 4 * h4, W = 4 * w4;
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i >= (long)H * W) return;
     logit4 += blockIdx.y * logit_gs;                     // frame blockIdx.y of a decode group
     agg += blockIdx.y * agg_gs;
-    const int oy = (int)(i / W), ox = (int)(i - (long)oy * W);
-    int y0, y1, x0, x1; float fy, fx;
-    bil(oy, 0.25f, h4, y0, y1, fy);
-    bil(ox, 0.25f, w4, x0, x1, fx);
-    const float w00 = (1.f - fy) * (1.f - fx), w01 = (1.f - fy) * fx, w10 = fy * (1.f - fx), w11 = fy * fx;
-    float p[MAXOBJ];
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < (long)H * W; i += (long)gridDim.x * 256) {
+        const int oy = (int)(i / W), ox = (int)(i - (long)oy * W);
+        int y0, y1, x0, x1; float fy, fx;
+        bil(oy, 0.25f, h4, y0, y1, fy);
+        bil(ox, 0.25f, w4, x0, x1, fx);
+        const float w00 = (1.f - fy) * (1.f - fx), w01 = (1.f - fy) * fx, w10 = fy * (1.f - fx), w11 = fy * fx;
+        float p[MAXOBJ];
 #pragma unroll
-    for (int o = 0; o < MAXOBJ; ++o) {
-        p[o] = 0.f;
-        if (o < k) {
-            const float *l = logit4 + (long)o * obj_stride;
-            const float v = w00 * l[y0 * w4 + x0] + w01 * l[y0 * w4 + x1] + w10 * l[y1 * w4 + x0] +
-                            w11 * l[y1 * w4 + x1];
-            p[o] = sigmoidf_(v);
+        for (int o = 0; o < MAXOBJ; ++o) {
+            p[o] = 0.f;
+            if (o < k) {
+                const float *l = logit4 + (long)o * obj_stride;
+                const float v = w00 * l[y0 * w4 + x0] + w01 * l[y0 * w4 + x1] + w10 * l[y1 * w4 + x0] +
+                                w11 * l[y1 * w4 + x1];
+                p[o] = sigmoidf_(v);
+            }
         }
-    }
-    if constexpr (AGG) {
-        aggregate_store<MAXOBJ>(p, k, agg, stride, i);
-    } else {
+        if constexpr (AGG) {
+            aggregate_store<MAXOBJ>(p, k, agg, stride, i);
+        } else {
 #pragma unroll
-        for (int o = 0; o < MAXOBJ; ++o)
-            if (o < k) agg[o * stride + i] = p[o];
+            for (int o = 0; o < MAXOBJ; ++o)
+                if (o < k) agg[o * stride + i] = p[o];
+        }
     }
 }
 void up4_sigmoid_aggregate_launch(const float *logit4, int k, int h4, int w4, float *agg, long agg_stride,
@@ -235,28 +238,28 @@ void up4_sigmoid_launch(const float *logit4, int k, int h4, int w4, float *prob,
 // 1000 before the softmax - odds^1000 is not representable, so that case takes the logarithm and the usual max-shifted softmax.
 template <int MAXOBJ>
 __global__ void aggregate_wbg_kernel(const float *__restrict__ prob, int k, long npix, int keep_bg, int hard, float *__restrict__ out) {
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i >= npix) return;
-    float p[MAXOBJ];
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < npix; i += (long)gridDim.x * 256) {
+        float p[MAXOBJ];
 #pragma unroll
-    for (int o = 0; o < MAXOBJ; ++o) p[o] = o < k ? prob[o * npix + i] : 0.f;
-    float odds[MAXOBJ + 1];
-    float tot = aggregate_odds<MAXOBJ>(p, k, odds);
-    if (hard) {
-        float mx = -INFINITY;
+        for (int o = 0; o < MAXOBJ; ++o) p[o] = o < k ? prob[o * npix + i] : 0.f;
+        float odds[MAXOBJ + 1];
+        float tot = aggregate_odds<MAXOBJ>(p, k, odds);
+        if (hard) {
+            float mx = -INFINITY;
 #pragma unroll
-        for (int o = 0; o <= MAXOBJ; ++o)
-            if (o <= k) { odds[o] = 1000.f * logf(odds[o]); mx = fmaxf(mx, odds[o]); }
-        tot = 0.f;
+            for (int o = 0; o <= MAXOBJ; ++o)
+                if (o <= k) { odds[o] = 1000.f * logf(odds[o]); mx = fmaxf(mx, odds[o]); }
+            tot = 0.f;
 #pragma unroll
-        for (int o = 0; o <= MAXOBJ; ++o)
-            if (o <= k) { odds[o] = expf(odds[o] - mx); tot += odds[o]; }
+            for (int o = 0; o <= MAXOBJ; ++o)
+                if (o <= k) { odds[o] = expf(odds[o] - mx); tot += odds[o]; }
+        }
+        const int up = keep_bg ? 0 : 1;                      // without the background row the object rows move up by one
+        if (keep_bg) out[i] = odds[0] / tot;
+#pragma unroll
+        for (int o = 1; o <= MAXOBJ; ++o)
+            if (o <= k) out[(o - up) * npix + i] = odds[o] / tot;
     }
-    const int up = keep_bg ? 0 : 1;                      // without the background row the object rows move up by one
-    if (keep_bg) out[i] = odds[0] / tot;
-#pragma unroll
-    for (int o = 1; o <= MAXOBJ; ++o)
-        if (o <= k) out[(o - up) * npix + i] = odds[o] / tot;
 }
 void aggregate_wbg_launch(const float *prob, int k, long npix, int keep_bg, int hard, float *out, hipStream_t s) {
     if (k <= 8)
@@ -269,12 +272,12 @@ void aggregate_wbg_launch(const float *prob, int k, long npix, int keep_bg, int 
 template <int MAXOBJ>
 __global__ void sigmoid_aggregate_kernel(const float *__restrict__ logit, int k, long npix,
                                          float *__restrict__ agg, long stride) {
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i >= npix) return;
-    float p[MAXOBJ];
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < npix; i += (long)gridDim.x * 256) {
+        float p[MAXOBJ];
 #pragma unroll
-    for (int o = 0; o < MAXOBJ; ++o) p[o] = o < k ? sigmoidf_(logit[o * npix + i]) : 0.f;
-    aggregate_store<MAXOBJ>(p, k, agg, stride, i);
+        for (int o = 0; o < MAXOBJ; ++o) p[o] = o < k ? sigmoidf_(logit[o * npix + i]) : 0.f;
+        aggregate_store<MAXOBJ>(p, k, agg, stride, i);
+    }
 }
 void sigmoid_aggregate_launch(const float *logit, int k, long npix, float *agg, long agg_stride, hipStream_t s) {
     if (k <= 8)
@@ -285,15 +288,15 @@ void sigmoid_aggregate_launch(const float *logit, int k, long npix, float *agg, 
 
 // final masks (inference_core.py:247-248): argmax over the k+1 rows, first maximum wins
 __global__ void argmax_kernel(const float *__restrict__ prob, int kk, int T, long npix, uint8_t *__restrict__ masks) {
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i >= (long)T * npix) return;
-    float best = prob[i];
-    int bi = 0;
-    for (int r = 1; r < kk; ++r) {
-        const float v = prob[(long)r * T * npix + i];
-        if (v > best) { best = v; bi = r; }
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < (long)T * npix; i += (long)gridDim.x * 256) {
+        float best = prob[i];
+        int bi = 0;
+        for (int r = 1; r < kk; ++r) {
+            const float v = prob[(long)r * T * npix + i];
+            if (v > best) { best = v; bi = r; }
+        }
+        masks[i] = (uint8_t)bi;
     }
-    masks[i] = (uint8_t)bi;
 }
 void argmax_launch(const float *prob, int kk, int T, long npix, uint8_t *masks, hipStream_t s) {
     hipLaunchKernelGGL(argmax_kernel, dim3(nblocks((long)T * npix)), dim3(256), 0, s, prob, kk, T, npix, masks);
@@ -303,17 +306,19 @@ void argmax_launch(const float *prob, int kk, int T, long npix, uint8_t *masks, 
 __global__ void rowsumsq_kernel(const float *__restrict__ x, int n, int C, float *__restrict__ out, long x_bs, long out_bs) {
     x += blockIdx.y * x_bs;                              // batch element blockIdx.y (consecutive key-cache slots)
     out += blockIdx.y * out_bs;
-    const long gt = blockIdx.x * 256L + threadIdx.x;
-    const long row = gt >> 4;
-    const int sub = (int)(gt & 15);
-    float acc = 0.f;
-    if (row < n)
-        for (int c = sub * 4; c < C; c += 64) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(x + row * C + c);
-            acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        }
-    for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if (row < n && sub == 0) out[row] = acc;
+    for (long g0 = blockIdx.x * 256L; g0 < (long)n * 16; g0 += (long)gridDim.x * 256) {      // uniform per workgroup: the 16 lanes of a row shuffle
+        const long gt = g0 + threadIdx.x;
+        const long row = gt >> 4;
+        const int sub = (int)(gt & 15);
+        float acc = 0.f;
+        if (row < n)
+            for (int c = sub * 4; c < C; c += 64) {
+                const f32x4 v = *reinterpret_cast<const f32x4 *>(x + row * C + c);
+                acc += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            }
+        for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        if (row < n && sub == 0) out[row] = acc;
+    }
 }
 void rowsumsq_launch(const float *x, int n, int C, float *out, hipStream_t s, int B, long x_bs, long out_bs) {
     hipLaunchKernelGGL(rowsumsq_kernel, dim3(nblocks((long)n * 16), B), dim3(256), 0, s, x, n, C, out, x_bs, out_bs);
@@ -328,18 +333,19 @@ void fill_launch(float *p, float v, long n, hipStream_t s) {
 
 __global__ void copy_rows_kernel(const float *__restrict__ src, long ss, float *__restrict__ dst, long ds, int rows,
                                  long n) {
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i >= rows * n) return;
-    const int r = (int)(i / n);
-    const long c = i - r * n;
-    dst[r * ds + c] = src[r * ss + c];
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < rows * n; i += (long)gridDim.x * 256) {
+        const int r = (int)(i / n);
+        const long c = i - r * n;
+        dst[r * ds + c] = src[r * ss + c];
+    }
 }
 // two contiguous copies in one launch: a [na floats, multiple of 4] -> da, b [nb floats] -> db (bank insertion: key rows + |mk|^2)
 __global__ void copy2_kernel(const float *__restrict__ a, float *__restrict__ da, long na4, const float *__restrict__ b, float *__restrict__ db,
                              long nb) {
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i < na4) reinterpret_cast<f32x4 *>(da)[i] = reinterpret_cast<const f32x4 *>(a)[i];
-    else if (i - na4 < nb) db[i - na4] = b[i - na4];
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < na4 + nb; i += (long)gridDim.x * 256) {
+        if (i < na4) reinterpret_cast<f32x4 *>(da)[i] = reinterpret_cast<const f32x4 *>(a)[i];
+        else if (i - na4 < nb) db[i - na4] = b[i - na4];
+    }
 }
 void copy2_launch(const float *a, float *da, long na, const float *b, float *db, long nb, hipStream_t s) {
     hipLaunchKernelGGL(copy2_kernel, dim3(nblocks(na / 4 + nb)), dim3(256), 0, s, a, da, na / 4, b, db, nb);
@@ -356,19 +362,19 @@ __global__ void interact_mask_kernel(const float *__restrict__ mask, int mc, int
                                      int lh, float *__restrict__ prob_idx, long prs, int kk,
                                      float *__restrict__ padded, float *__restrict__ pos, float *__restrict__ neg) {
     const long npix = (long)nh * nw;
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i >= npix) return;
-    const int y = (int)(i / nw), x = (int)(i - (long)y * nw);
-    const int sy = y - lh, sx = x - lw;
-    const bool in = (unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W;
-    for (int c = 0; c < mc; ++c) padded[c * npix + i] = in ? mask[((long)c * H + sy) * W + sx] : 0.f;
-    for (int r = 0; r < kk; ++r) {
-        const int c = mc == 1 ? 0 : r;                    // torch broadcasting of a 1-channel mask
-        const float m = in ? mask[((long)c * H + sy) * W + sx] : 0.f;
-        const float d = m - prob_idx[r * prs + i];
-        pos[r * npix + i] = fminf(fmaxf(d, 0.f), 1.f);
-        neg[r * npix + i] = fminf(fmaxf(-d, 0.f), 1.f);
-        prob_idx[r * prs + i] = m;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < npix; i += (long)gridDim.x * 256) {
+        const int y = (int)(i / nw), x = (int)(i - (long)y * nw);
+        const int sy = y - lh, sx = x - lw;
+        const bool in = (unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W;
+        for (int c = 0; c < mc; ++c) padded[c * npix + i] = in ? mask[((long)c * H + sy) * W + sx] : 0.f;
+        for (int r = 0; r < kk; ++r) {
+            const int c = mc == 1 ? 0 : r;                    // torch broadcasting of a 1-channel mask
+            const float m = in ? mask[((long)c * H + sy) * W + sx] : 0.f;
+            const float d = m - prob_idx[r * prs + i];
+            pos[r * npix + i] = fminf(fmaxf(d, 0.f), 1.f);
+            neg[r * npix + i] = fminf(fmaxf(-d, 0.f), 1.f);
+            prob_idx[r * prs + i] = m;
+        }
     }
 }
 void interact_mask_launch(const float *mask, int mc, int H, int W, int nh, int nw, int lw, int lh,
@@ -382,15 +388,15 @@ void interact_mask_launch(const float *mask, int mc, int H, int W, int nh, int n
 __global__ void pack_fusion_input_kernel(const float *__restrict__ img4, const float *__restrict__ prev,
                                          const float *__restrict__ curr, const float *__restrict__ attn2, float nc,
                                          float nr, long npix, float *__restrict__ out) {
-    const long i = blockIdx.x * 256L + threadIdx.x;
-    if (i >= npix) return;
-    const f32x4 im = *reinterpret_cast<const f32x4 *>(img4 + i * 4);
-    const f32x4 a = {im.x, im.y, im.z, prev[i]};
-    const f32x4 b = {curr[i], attn2[i], attn2[npix + i], nc};
-    const f32x4 c = {nr, 0.f, 0.f, 0.f};
-    *reinterpret_cast<f32x4 *>(out + i * 12) = a;
-    *reinterpret_cast<f32x4 *>(out + i * 12 + 4) = b;
-    *reinterpret_cast<f32x4 *>(out + i * 12 + 8) = c;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < npix; i += (long)gridDim.x * 256) {
+        const f32x4 im = *reinterpret_cast<const f32x4 *>(img4 + i * 4);
+        const f32x4 a = {im.x, im.y, im.z, prev[i]};
+        const f32x4 b = {curr[i], attn2[i], attn2[npix + i], nc};
+        const f32x4 c = {nr, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4 *>(out + i * 12) = a;
+        *reinterpret_cast<f32x4 *>(out + i * 12 + 4) = b;
+        *reinterpret_cast<f32x4 *>(out + i * 12 + 8) = c;
+    }
 }
 void pack_fusion_input_launch(const float *img4, const float *prev, const float *curr, const float *attn2,
                               float nc, float nr, long npix, float *out, hipStream_t s) {
@@ -465,54 +471,54 @@ __global__ __launch_bounds__(512) void cbam_mlp_kernel(const float *__restrict__
 
 __global__ __launch_bounds__(256) void cbam_spool_kernel(const float *__restrict__ x, const float *__restrict__ gate,
                                                          int hw, long total, float *__restrict__ sp) {
-    const long gw = (blockIdx.x * 256L + threadIdx.x) >> 6;   // one wave per (b, pixel)
     const int lane = threadIdx.x & 63;
-    if (gw >= total) return;
-    const int b = (int)(gw / hw);
-    const float *xp = x + gw * 512 + lane * 8;
-    const float *g = gate + (long)b * 512 + lane * 8;
-    const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xp), a1 = *reinterpret_cast<const f32x4 *>(xp + 4);
-    const f32x4 g0 = *reinterpret_cast<const f32x4 *>(g), g1 = *reinterpret_cast<const f32x4 *>(g + 4);
-    const float v[8] = {a0.x * g0.x, a0.y * g0.y, a0.z * g0.z, a0.w * g0.w,
-                        a1.x * g1.x, a1.y * g1.y, a1.z * g1.z, a1.w * g1.w};
-    float mx = v[0], sum = v[0];
+    for (long gw = (blockIdx.x * 256L + threadIdx.x) >> 6; gw < total; gw += (long)gridDim.x * 4) {      // one wave per (b, pixel)
+        const int b = (int)(gw / hw);
+        const float *xp = x + gw * 512 + lane * 8;
+        const float *g = gate + (long)b * 512 + lane * 8;
+        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(xp), a1 = *reinterpret_cast<const f32x4 *>(xp + 4);
+        const f32x4 g0 = *reinterpret_cast<const f32x4 *>(g), g1 = *reinterpret_cast<const f32x4 *>(g + 4);
+        const float v[8] = {a0.x * g0.x, a0.y * g0.y, a0.z * g0.z, a0.w * g0.w,
+                            a1.x * g1.x, a1.y * g1.y, a1.z * g1.z, a1.w * g1.w};
+        float mx = v[0], sum = v[0];
 #pragma unroll
-    for (int i = 1; i < 8; ++i) { mx = fmaxf(mx, v[i]); sum += v[i]; }
-    for (int o = 32; o > 0; o >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, o));
-        sum += __shfl_xor(sum, o);
+        for (int i = 1; i < 8; ++i) { mx = fmaxf(mx, v[i]); sum += v[i]; }
+        for (int o = 32; o > 0; o >>= 1) {
+            mx = fmaxf(mx, __shfl_xor(mx, o));
+            sum += __shfl_xor(sum, o);
+        }
+        if (lane == 0) { sp[gw * 2] = mx; sp[gw * 2 + 1] = sum * (1.f / 512.f); }
     }
-    if (lane == 0) { sp[gw * 2] = mx; sp[gw * 2 + 1] = sum * (1.f / 512.f); }
 }
 
 __global__ __launch_bounds__(256) void cbam_apply_kernel(const float *__restrict__ x, const float *__restrict__ gate,
                                                          const float *__restrict__ sp, CbamW cw, int h, int w,
                                                          long total, float *__restrict__ out) {
-    const long gw = (blockIdx.x * 256L + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
-    if (gw >= total) return;
-    const int hw = h * w;
-    const int b = (int)(gw / hw), pix = (int)(gw - (long)b * hw);
-    const int py = pix / w, px = pix - py * w;
-    float acc = 0.f;
-    if (lane < 49) {
-        const int ky = lane / 7, kx = lane - ky * 7;
-        const int iy = py + ky - 3, ix = px + kx - 3;
-        if ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) {
-            const float *q = sp + ((long)b * hw + iy * w + ix) * 2;
-            acc = cw.wsp[lane] * q[0] + cw.wsp[49 + lane] * q[1];   // wsp [2][7][7]: channel 0 = max, 1 = mean
+    for (long gw = (blockIdx.x * 256L + threadIdx.x) >> 6; gw < total; gw += (long)gridDim.x * 4) {      // one wave per (b, pixel)
+        const int hw = h * w;
+        const int b = (int)(gw / hw), pix = (int)(gw - (long)b * hw);
+        const int py = pix / w, px = pix - py * w;
+        float acc = 0.f;
+        if (lane < 49) {
+            const int ky = lane / 7, kx = lane - ky * 7;
+            const int iy = py + ky - 3, ix = px + kx - 3;
+            if ((unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w) {
+                const float *q = sp + ((long)b * hw + iy * w + ix) * 2;
+                acc = cw.wsp[lane] * q[0] + cw.wsp[49 + lane] * q[1];   // wsp [2][7][7]: channel 0 = max, 1 = mean
+            }
         }
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        const float sg = sigmoidf_(acc + cw.bsp);
+        const float *xp = x + gw * 512 + lane * 8;
+        const float *g = gate + (long)b * 512 + lane * 8;
+        f32x4 a0 = *reinterpret_cast<const f32x4 *>(xp), a1 = *reinterpret_cast<const f32x4 *>(xp + 4);
+        const f32x4 g0 = *reinterpret_cast<const f32x4 *>(g), g1 = *reinterpret_cast<const f32x4 *>(g + 4);
+        a0.x += a0.x * g0.x * sg; a0.y += a0.y * g0.y * sg; a0.z += a0.z * g0.z * sg; a0.w += a0.w * g0.w * sg;
+        a1.x += a1.x * g1.x * sg; a1.y += a1.y * g1.y * sg; a1.z += a1.z * g1.z * sg; a1.w += a1.w * g1.w * sg;
+        *reinterpret_cast<f32x4 *>(out + gw * 512 + lane * 8) = a0;
+        *reinterpret_cast<f32x4 *>(out + gw * 512 + lane * 8 + 4) = a1;
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    const float sg = sigmoidf_(acc + cw.bsp);
-    const float *xp = x + gw * 512 + lane * 8;
-    const float *g = gate + (long)b * 512 + lane * 8;
-    f32x4 a0 = *reinterpret_cast<const f32x4 *>(xp), a1 = *reinterpret_cast<const f32x4 *>(xp + 4);
-    const f32x4 g0 = *reinterpret_cast<const f32x4 *>(g), g1 = *reinterpret_cast<const f32x4 *>(g + 4);
-    a0.x += a0.x * g0.x * sg; a0.y += a0.y * g0.y * sg; a0.z += a0.z * g0.z * sg; a0.w += a0.w * g0.w * sg;
-    a1.x += a1.x * g1.x * sg; a1.y += a1.y * g1.y * sg; a1.z += a1.z * g1.z * sg; a1.w += a1.w * g1.w * sg;
-    *reinterpret_cast<f32x4 *>(out + gw * 512 + lane * 8) = a0;
-    *reinterpret_cast<f32x4 *>(out + gw * 512 + lane * 8 + 4) = a1;
 }
 
 void cbam_launch(const float *x, float *out, int B, int h, int w, const CbamW &cw, float *scratch, hipStream_t s) {

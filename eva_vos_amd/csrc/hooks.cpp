@@ -94,6 +94,7 @@ struct ReadRig {
              float sigma, int32_t *centres, int32_t *topk_idx, float *topk_w, float *readout) {
         const bool bad = !mk || !mv || !qk || !readout || top_k < 1 || top_k > STCN_MAX_TOP_K || N < top_k || Q < 1 || k < 1;
         if (bad) { set_error("%s: bad arguments (1 <= top_k <= %d, N >= top_k; top_k=%d N=%d)", who, STCN_MAX_TOP_K, top_k, N); return STCN_E_INVALID; }
+        if (N >= MEMREAD_MAX_ROWS) { set_error("%s: a bank of N=%d rows, the read addresses fewer than 2^24 = %ld", who, N, MEMREAD_MAX_ROWS); return STCN_E_INVALID; }
         const bool with_km = h16 != 0 || w16 != 0 || sigma != 0.f || centres;      // all zero: the plain read
         // the kernelized read: km > 0 finite, the Q queries whole frames of h16 x w16 positions (16-bit coordinates)
         const bool km_ok = std::isfinite(sigma) && sigma > 0.f && h16 >= 1 && w16 >= 1 && h16 < 32768 && w16 < 32768 && (long)h16 * w16 <= Q && Q % (h16 * w16) == 0;
@@ -209,6 +210,7 @@ int stcn_test_conv_plan(int B, int H, int W, int Cin, int Cout, int K, int strid
         q.mb, q.tiles_m, q.tiles_n, q.grid, q.full_wg, q.pieces, q.per, q.chunks, q.tm_per_chunk,
         direct ? p.tile_big : 0, direct ? p.rem_full : 0, direct ? p.rem_split : 0, direct ? p.rem_per : 0, direct ? p.chain : 0};
     for (int i = 0; i < STCN_CONV_PLAN_INTS; ++i) iv[i] = v[i];
+    if (n > STCN_CONV_PLAN_INTS) iv[STCN_CONV_PLAN_INTS] = direct ? p.affine_out : 0;
     dv[0] = (double)pl.v_floats; dv[1] = pl.fl_exec;
     return STCN_OK;
 }

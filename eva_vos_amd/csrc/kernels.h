@@ -238,6 +238,8 @@ MemReadCost memread_cost(int N, int Q, int k, int top_k, bool km);
 struct MemReadScratch { float *cand_v; int32_t *cand_i; int32_t *cand_n; float *gmax; float *tau; };
 struct MemReadScratchSizes { size_t cand_v, cand_i, cand_n, gmax, tau; };
 MemReadScratchSizes memread_scratch_floats(int Q);
+constexpr long MAX_FRAME_PIXELS = 1L << 24;      // padded frame nh * nw an engine or a stage context is created for: the per-frame launches size their grids in 32 bits
+constexpr long MEMREAD_MAX_ROWS = 1L << 24;      // bank rows of one read: the read kernels build their key descriptor as (unsigned)N * 256 bytes, which wraps there
 constexpr int MEMREAD_MSQ_PAD = 64;     // readable floats behind the N values of msq: the read kernels fetch |mk|^2 in whole 64-row steps
 // dynamic LDS above 64 KB has to be opted into once per (device, kernel function)
 void allow_big_lds(const void *kernel, size_t lds);

@@ -86,6 +86,7 @@ extern "C" {
 
 int stcn_stage_create(const stcn_model *m, int nh, int nw, int max_objects, void *stream, stcn_stage **out) {
     if (nh < 16 || nw < 16 || nh % 16 || nw % 16) { set_error("stcn_stage_create: nh=%d nw=%d must be positive multiples of 16 (frames arrive padded)", nh, nw); return STCN_E_INVALID; }
+    if ((long)nh * nw > MAX_FRAME_PIXELS) { set_error("stcn_stage_create: a frame of nh=%d x nw=%d pixels, at most 2^24 = %ld", nh, nw, MAX_FRAME_PIXELS); return STCN_E_INVALID; }
     if (max_objects < 1 || max_objects > STCN_MAX_OBJECTS) { set_error("stcn_stage_create: max_objects=%d outside 1..%d", max_objects, STCN_MAX_OBJECTS); return STCN_E_INVALID; }
     if (!m || !out) { set_error("stcn_stage_create: null arguments"); return STCN_E_INVALID; }
     HIPCHK(hipSetDevice(m->m.device));
@@ -154,7 +155,8 @@ int stcn_stage_segment(stcn_stage *s, const float *mk16, long mk_plane_stride, c
     if (!mk16 || !mv16 || !qf8 || !qf4 || !qk16 || !qv16 || !prob) { set_error("%s: null arguments", who); return STCN_E_INVALID; }
     const Dims &d = s->w.d;
     const long N = (long)T * d.hw16;
-    if (N > (1L << 30) || mk_plane_stride < N || mv_plane_stride < N || mv_object_stride < 0) {
+    if (N >= MEMREAD_MAX_ROWS) { set_error("%s: a memory of T * h16 * w16 = %ld rows, the read addresses fewer than 2^24 = %ld", who, N, MEMREAD_MAX_ROWS); return STCN_E_INVALID; }
+    if (mk_plane_stride < N || mv_plane_stride < N || mv_object_stride < 0) {
         set_error("%s: bad strides (plane strides >= T * h16 * w16 = %ld; mk %ld, mv %ld)", who, N, mk_plane_stride, mv_plane_stride);
         return STCN_E_INVALID;
     }

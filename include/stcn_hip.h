@@ -233,7 +233,8 @@ int stcn_test_conv_path(int B, int H, int W, int Cin, int Cout, int K, int strid
  *   Winograd tile geometry TH, TW, Mt, Mt_pad, KB, and F(2x2)'s kb_per_split;
  *   F(4x4): mb, tiles_m, tiles_n, grid, full_wg, pieces, per, chunks, tm_per_chunk;
  *   direct: tile_big, rem_full, rem_split, rem_per, chain
- * - fields of other families than the plan's are zero.  dv (2 doubles): v_floats, fl_exec. */
+ * - fields of other families than the plan's are zero - and, only when n > STCN_CONV_PLAN_INTS, one more: affine_out (direct: the dense
+ * [M][N] epilogue through buffer descriptors, (M + 128) * N * 4 < 2^32).  dv (2 doubles): v_floats, fl_exec. */
 #define STCN_CONV_PLAN_INTS 27
 int stcn_test_conv_plan(int B, int H, int W, int Cin, int Cout, int K, int stride, int flags, int splitk, int32_t *iv, int n, double *dv);
 /* Which kernel family the calling thread's last convolution (stcn_test_conv, or the last conv an interact() enqueued) ran as:
@@ -285,7 +286,8 @@ int stcn_test_encode_value(const stcn_model *m, void *stream, const float *img, 
                            const float *masks, int k, int nh, int nw, float *out);
 
 /* Space-time memory read (prop_net.py:80-115 with the top-50 softmax of :53-60).
- * mk [N,64], mv [k,N,512], qk [Q,64] -> topk_idx [Q,50] (int32), topk_w [Q,50], readout [k,Q,512]. */
+ * mk [N,64], mv [k,N,512], qk [Q,64] -> topk_idx [Q,50] (int32), topk_w [Q,50], readout [k,Q,512].  N < 2^24 rows (the kernels' key descriptor
+ * counts bytes in 32 bits): a larger bank is refused with STCN_E_INVALID here, in stcn_stage_segment and where the engine's bank grows. */
 int stcn_test_memory_read(void *stream, const float *mk, const float *mv, const float *qk,
                           int N, int Q, int k, int32_t *topk_idx, float *topk_w, float *readout);
 /* The same read with the cut given (softmax_w_top(x, top=top_k), prop_net.py:53-60): 1 <= top_k <= STCN_MAX_TOP_K, N >= top_k;

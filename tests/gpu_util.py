@@ -73,3 +73,33 @@ def torch_aggregate_wbg(prob, keep_bg=False, hard=False):
     if hard:
         logits = logits * 1000
     return F.softmax(logits, dim=0) if keep_bg else F.softmax(logits, dim=0)[1:]
+
+
+# ---- shared by test_gpu_small_kernels.py and test_gpu_large_extents.py
+EPS = 2.0 ** -24
+
+
+def taps(n_out, n_in, scale):
+    """Source indices of F.interpolate(mode="bilinear", align_corners=False) per output index."""
+    s = ((torch.arange(n_out, dtype=torch.float64) + 0.5) * scale - 0.5).clamp(min=0)
+    i0 = s.floor().long().clamp(max=n_in - 1)
+    return i0, (i0 + 1).clamp(max=n_in - 1)
+
+
+def tap_max(a, scale):
+    """max |a| over the four bilinear taps of every output pixel; a [..., h, w]."""
+    h, w = a.shape[-2:]
+    (y0, y1), (x0, x1) = taps(round(h / scale), h, scale), taps(round(w / scale), w, scale)
+    a = a.abs()
+    return torch.stack([a[..., ys, :][..., xs] for ys in (y0, y1) for xs in (x0, x1)]).amax(0)
+
+
+def up4_prob(logit):
+    """logit [..., h4, w4] (3 leading dimensions at most) -> sigmoid(bilinear x4), in the precision of `logit`."""
+    lead = logit.shape[:-2]
+    p = torch.sigmoid(F.interpolate(logit.reshape(1, -1, *logit.shape[-2:]), scale_factor=4, mode="bilinear", align_corners=False))
+    return p.reshape(*lead, *p.shape[-2:])
+
+
+def aggregate_bound(figure):
+    return max(1e-6, 4 * figure)

@@ -35,6 +35,33 @@ def test_null_arguments_are_rejected_without_touching_the_gpu():
     assert lib.stcn_model_destroy(None) == 0 and lib.stcn_engine_destroy(None) == 0
 
 
+def test_a_bank_of_2_pow_24_rows_is_refused_before_any_device_call():
+    """The read kernels build the key descriptor as (unsigned)N * 256 bytes, which wraps at N = 2^24: every place that fills a read refuses such
+    a bank (MEMREAD_MAX_ROWS) - here the rig of the memory-read hooks, test and bench, plain and kernelized, on the host before anything is
+    allocated; the stage call: test_gpu_large_extents.py (its row count needs a context)."""
+    import ctypes as C
+    lib = _lib.lib()
+    one, ms = C.c_void_p(16), C.c_float()
+    for N in (1 << 24, (1 << 24) + 1620, (1 << 31) - 1):
+        assert lib.stcn_test_memory_read(None, one, one, one, N, 97, 1, None, None, one) == -1
+        assert f"N={N} rows" in lib.stcn_last_error().decode() and "2^24" in lib.stcn_last_error().decode()
+        assert lib.stcn_test_memory_read_km(None, one, one, one, N, 70, 2, 20, 7, 10, 4.0, None, None, None, one) == -1 and b"2^24" in lib.stcn_last_error()
+        assert lib.stcn_bench_memory_read_k(None, one, one, one, N, 97, 1, 20, 1, one, C.byref(ms), None) == -1 and b"2^24" in lib.stcn_last_error()
+
+
+def test_a_frame_beyond_2_pow_24_padded_pixels_is_refused_at_creation():
+    """The per-frame launches size their grids in 32 bits (MAX_FRAME_PIXELS): the engine and the stage context refuse such a frame on the host,
+    before the model is looked at; 4096 x 4096 is the largest square."""
+    import ctypes as C
+    lib = _lib.lib()
+    one, h = C.c_void_p(16), C.c_void_p()
+    for H, W in ((4096, 4112), (4097, 4096), (16, 1 << 21)):
+        assert lib.stcn_engine_create(one, 5, H, W, 1, 5, None, one, one, one, C.byref(h)) == -1
+        assert f"{H} x {W}" in lib.stcn_last_error().decode() and "2^24" in lib.stcn_last_error().decode()
+    assert lib.stcn_stage_create(one, 4096, 4112, 1, None, C.byref(h)) == -1 and b"2^24" in lib.stcn_last_error()
+    assert h.value is None
+
+
 def documented_small_kernels():
     """name -> (pointers, integers, doubles) as the comment above stcn_test_kernel in the header lists them: 'name  ptrs a, b  iv c, d  fv e'."""
     src = open(os.path.join(ROOT, "include", "stcn_hip.h")).read()

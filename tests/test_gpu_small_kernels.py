@@ -8,12 +8,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import dev, guard_intact, guarded, kernel, torch_aggregate_wbg
+from gpu_util import EPS, aggregate_bound, dev, guard_intact, guarded, kernel, tap_max, torch_aggregate_wbg, up4_prob
 from oracle import stcn_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-EPS = 2.0 ** -24
 KG = [(3, 2), (2, 3), (1, 4)]       # batches B = k * G laid out [object][frame]
 
 
@@ -44,21 +43,6 @@ def test_maxpool_equals_max_pool2d_on_negative_inputs(H, W, C, B):
 
 
 # ------------------------------------------------------------------------------------------------ upsample2x_add
-def taps(n_out, n_in, scale):
-    """Source indices of F.interpolate(mode="bilinear", align_corners=False) per output index."""
-    s = ((torch.arange(n_out, dtype=torch.float64) + 0.5) * scale - 0.5).clamp(min=0)
-    i0 = s.floor().long().clamp(max=n_in - 1)
-    return i0, (i0 + 1).clamp(max=n_in - 1)
-
-
-def tap_max(a, scale):
-    """max |a| over the four bilinear taps of every output pixel; a [..., h, w]."""
-    h, w = a.shape[-2:]
-    (y0, y1), (x0, x1) = taps(round(h / scale), h, scale), taps(round(w / scale), w, scale)
-    a = a.abs()
-    return torch.stack([a[..., ys, :][..., xs] for ys in (y0, y1) for xs in (x0, x1)]).amax(0)
-
-
 UPS = [(h, w, C, form) for (h, w) in [(1, 1), (1, 5), (3, 2), (7, 9)] for C in (4, 256, 512) for form in ("dense", "broadcast", "frames")]
 
 
@@ -98,13 +82,6 @@ def test_upsample2x_add_matches_interpolate_plus_skip(h, w, C, form):
 
 
 # ------------------------------------------------------------------------------------------------ decoder tail
-def up4_prob(logit):
-    """logit [..., h4, w4] (3 leading dimensions at most) -> sigmoid(bilinear x4), in the precision of `logit`."""
-    lead = logit.shape[:-2]
-    p = torch.sigmoid(F.interpolate(logit.reshape(1, -1, *logit.shape[-2:]), scale_factor=4, mode="bilinear", align_corners=False))
-    return p.reshape(*lead, *p.shape[-2:])
-
-
 # wide: the frames' agg blocks further apart than (k + 1) rows - only at G > 1: a one-frame launch never reads agg_gs.  The launch itself has no
 # default for it (0 at G > 1 would lay the frames over each other); the engine's default, (k + 1) * agg_stride, is what the cases that are not wide pass
 UP4 = [(k, G, hw, wide) for k in (1, 3, 8, 9, 32) for G in (1, 3) for hw in [(1, 1), (4, 4), (5, 7)] for wide in (False, True) if G > 1 or not wide]
@@ -122,10 +99,6 @@ def up4_case(k, G, h4, w4):
 def fp32_figure(k):
     """The largest error of the formula in torch fp32 on the CPU against fp64 over the cases of k objects: no kernel output enters it."""
     return max(float((f32.double() - ref).abs().max()) for kc, G, (h4, w4), wide in UP4 if kc == k and not wide for _, ref, f32 in [up4_case(k, G, h4, w4)])
-
-
-def aggregate_bound(figure):
-    return max(1e-6, 4 * figure)
 
 
 @pytest.mark.parametrize("k,G,hw,wide", UP4)

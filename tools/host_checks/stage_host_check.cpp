@@ -46,6 +46,10 @@ int main() {
     EXPECT(stcn_fusion_model_create(0, &d, 1, &m) == STCN_E_INVALID && says("descriptor") && !m);      // a descriptor without name / data
     EXPECT(stcn_test_transpose(nullptr, p, p, 1, 8, 6, 8, 0, 1) == STCN_E_INVALID);
     EXPECT(stcn_test_transpose(nullptr, p, p, 1, 8, 4, 7, 0, 1) == STCN_E_INVALID);
+    // a bank of 2^24 rows (the read kernels' key descriptor, (unsigned)N * 256 bytes, wraps there) is refused where the hooks fill a read
+    EXPECT(stcn_test_memory_read(nullptr, p, p, p, 1 << 24, 97, 1, nullptr, nullptr, p) == STCN_E_INVALID && says("2^24"));
+    float ms = 0.f;
+    EXPECT(stcn_bench_memory_read(nullptr, p, p, p, 1 << 24, 97, 1, 1, p, &ms, nullptr) == STCN_E_INVALID && says("2^24"));
     // the bank staging: never shrinks, holds what is asked, and a memory growing one frame per call (80 rows at a time up to 100 frames)
     // allocates a logarithmic number of times
     EXPECT(stcn::stage_grow(0, 80) == 80 && stcn::stage_grow(80, 80) == 80 && stcn::stage_grow(80, 10) == 80 && stcn::stage_grow(80, 81) == 160 && stcn::stage_grow(80, 1000) == 1000);
