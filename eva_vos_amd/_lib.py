@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # STCN_LIB: another build of the same library (measurement aid: tools/gpu_ab_trace.sh compares two builds on one GPU box)
 LIB_PATH = os.environ.get("STCN_LIB") or os.path.join(_HERE, "libstcn_hip.so")
 
+RESET_KEEP_FRAMES = 1          # STCN_RESET_KEEP_FRAMES (stcn_engine_reset_ex)
 K_CLASSES = ("conv", "conv_reduce", "memread", "elementwise", "conv_n1", "other", "wino_input", "fusion_conv", "attention")
 
 
@@ -61,9 +62,11 @@ PROTOTYPES = {
     "stcn_engine_get_opts": (_I, [_P, C.POINTER(EngineOpts)]),
     "stcn_engine_destroy": (_I, [_P]),
     "stcn_engine_reset": (_I, [_P]),
+    "stcn_engine_reset_ex": (_I, [_P, C.c_uint32, C.POINTER(C.c_int32)]),
     "stcn_engine_clone": (_I, [_P, _P, _P, _P, C.POINTER(_P)]),
     "stcn_interact": (_I, [_P, _P, _I, _I, _I]),
     "stcn_get_stats": (_I, [_P, C.POINTER(Stats)]),
+    "stcn_get_key_frames": (_I, [_P, C.POINTER(C.c_int64)]),
     "stcn_get_flops": (_I, [_P, C.POINTER(_D)]),
     "stcn_last_conv_path": (C.c_char_p, []),
     "stcn_test_conv_trace": (_I, [_I]),

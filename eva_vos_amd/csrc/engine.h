@@ -244,6 +244,7 @@ struct stcn_engine {
     int group = 1;                       // frames per memory-read + decoder pass (env STCN_DECODE_BATCH), <= MAX_DECODE_GROUP
     stcn::Prof prof;
     stcn_stats stats{};
+    int64_t key_frames = 0;              // frames that went through the key encoder since creation / the last reset (stcn_get_key_frames)
     std::string failed;                  // non-empty: a failed interaction left prob / masks half-written (see stcn_interact)
     std::vector<void *> allocs;
 };

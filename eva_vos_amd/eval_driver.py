@@ -12,6 +12,8 @@ Differences by design:
 * J / J&F per frame come from the device (``stcn_metrics_jf_counts``) - masks never visit the host per round;
 * QNet frame selection keeps features on the device (``eva_vos_amd.qnet``);
 * two samples are in flight per GPU (host thread + HIP stream each, ``--lanes``): +9..17 % rounds/s;
+* the per-object sessions of a video share one engine and the frame features it has computed (``fq_driver.LaneCores``; same rows;
+  ``--no-share-frames`` switches it off), so videos, not samples, are dealt to ranks and lanes;
 * samples are LPT-sharded over ranks instead of ``--min-idx/--max-idx``; ONE gather of fixed-width rows at the end
   (RCCL over xGMI), rank 0 writes the CSV with the reference's columns ``video, mu_metric, annotation_time, round``;
 * ``--multi-object`` (an additional mode; the reference's per-object protocol stays the default): ONE session per video with all its
@@ -34,7 +36,7 @@ import numpy as np
 import torch
 
 from . import metrics, shard
-from .fq_driver import NO_OBJECT, ClipDataset, annotation_session, frame_quality, lane_engine_options, run_lanes
+from .fq_driver import NO_OBJECT, ClipDataset, LaneCores, annotation_session, frame_quality, lane_engine_options, run_lanes
 
 POLICIES = ("oracle_mask", "rand_mask", "qnet_mask", "upper_bound_mask")
 MULTI_OBJECT_POLICIES = ("oracle_mask", "rand_mask")          # QNet takes one binary mask; the upper bound builds on the one-object scorer
@@ -119,10 +121,14 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
 
 def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "oracle_mask", rounds: int = 60,
         metric: str = "j_and_f", qnet=None, seed: int = 0, device: str = "cuda", lanes: int = 2, stats: dict = None,
-        multi_object: bool = False):
+        multi_object: bool = False, share_frames: bool = True):
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
     (rows: sample id, round, mu_metric, annotation_time, annotated frame, T, then T per-frame values, NaN-padded).
-    `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited) and `interactions` are added to it.
+    `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited), `interactions`, `key_frames_encoded` (frames that
+    went through the key encoder) and `engines_created` are added to it.
+    `share_frames` (per-object mode; the protocol and the rows stay the reference's): the sessions of a video's objects run one after the
+    other on ONE engine that keeps the clip and its frame features between them (fq_driver.LaneCores) - videos, not samples, are dealt to
+    ranks and lanes.  False: a fresh engine and a fresh upload per sample, samples dealt one by one.
     `multi_object`: one session per VIDEO with all its objects in one engine.  The rows keep their schema and the sample ids of the per-object
     enumeration, one per (video, object, round), so the outputs of the two modes join on (sample id, round): mu_metric = the mean of that
     object's quality over the frames where it is present, annotation_time = 80 s if the object is present in the annotated frame, else
@@ -139,16 +145,23 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         if k > MAX_OBJECTS:
             raise ValueError(f"video {v} has {k} objects: a multi-object session holds at most {MAX_OBJECTS}")
     t_max = max(s[2] for s in ds.samples)
-    mine = sorted(shard.lpt_assign([s[2] * (s[1] if multi_object else 1) for s in ds.samples], world)[rank])      # multi-object: frames x objects
+    share_frames = share_frames and not multi_object
+    if share_frames:
+        mine = sorted(shard.lpt_assign_grouped([s[2] for s in ds.samples], [s[0] for s in ds.samples], world)[rank])      # the objects of a video share an engine
+    else:
+        mine = sorted(shard.lpt_assign([s[2] * (s[1] if multi_object else 1) for s in ds.samples], world)[rank])      # multi-object: frames x objects
+    cores = LaneCores(lambda sample: InferenceCore(prop_net, fuse_net, sample["rgb"], sample["num_objects"] if multi_object else 1,
+                                                   engine_options=lane_engine_options(lanes)), share_frames)
     width = 6 + t_max
     stats_lock = __import__("threading").Lock()
 
     def work(i, sample):
         rows = []
         t_c = time.perf_counter()
-        proc = InferenceCore(prop_net, fuse_net, sample["rgb"], sample["num_objects"] if multi_object else 1, engine_options=lane_engine_options(lanes))
+        proc = cores.core_for(sample)
         t_s = time.perf_counter()
         res = run_policy(policy, proc, sample, rounds, metric, qnet, random.Random(seed * 100003 + i), multi_object=multi_object)
+        cores.done(proc)
         if stats is not None:
             with stats_lock:
                 stats["create_s"] = stats.get("create_s", 0.0) + t_s - t_c
@@ -172,7 +185,9 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
             rows.append(row)
         return rows
 
-    rows = run_lanes(root, imset, mine, lanes, work, device, stats, per_video=multi_object)
+    rows = run_lanes(root, imset, mine, lanes, work, device, stats, per_video=multi_object, share_frames=share_frames, lane_done=cores.release)
+    if stats is not None:
+        cores.add_to(stats)
     allrows = shard.gather_rows(np.stack(rows) if rows else np.zeros((0, width), np.float32), width)
     if rank == 0 and out_csv:
         os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
@@ -194,6 +209,8 @@ def main():
     ap.add_argument("--lanes", type=int, default=2, help="videos in flight per GPU")
     ap.add_argument("--multi-object", action="store_true", help="one session per video with all its objects in one engine (policies: "
                     + ", ".join(MULTI_OBJECT_POLICIES) + "); default: one session per (video, object), the reference's protocol")
+    ap.add_argument("--no-share-frames", action="store_true", help="per-object mode: a fresh engine and a fresh upload of the clip for every object "
+                    "of a video (default: the sessions of a video's objects share one engine and its frame features; same output)")
     ap.add_argument("--db", default="MOSE")
     ap.add_argument("--prop-weights", default="./model_weights/mivos/stcn.pth")
     ap.add_argument("--fusion-weights", default="./model_weights/mivos/fusion.pth")
@@ -226,7 +243,8 @@ def main():
     if qnet is not None:
         qnet = qnet.cuda().eval()
     out = os.path.join("Experiments", a.db, f"{a.policy}.csv")
-    rows = run(a.root, a.imset, out, prop.eval(), fuse.eval(), a.policy, a.rounds, qnet=qnet, lanes=a.lanes, multi_object=a.multi_object)
+    rows = run(a.root, a.imset, out, prop.eval(), fuse.eval(), a.policy, a.rounds, qnet=qnet, lanes=a.lanes, multi_object=a.multi_object,
+               share_frames=not a.no_share_frames)
     if not dist.is_initialized() or dist.get_rank() == 0:
         print(f"{len(rows)} rounds -> {out}")
     if dist.is_initialized():

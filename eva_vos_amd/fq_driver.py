@@ -10,6 +10,9 @@ the writer ``util/fq_dataset.py:50-91`` (224x224 nearest-resized masks as PNG + 
 * samples are assigned to ranks with an LPT schedule over their frame counts instead of ``--min-idx/--max-idx``;
   propagation has no collective; ONE gather of fixed-width rows at the end (RCCL over xGMI), rank 0 writes the CSV;
 * a decoded clip is cached per video and reused for all its objects (the reference re-decodes it per object);
+* so are its device copy and the engine with the frame features it has computed: the sessions of a video's objects run one after the other
+  on one ``InferenceCore`` re-targeted with ``reset(keep_frame_features=True)``, videos are dealt whole to ranks and lanes - same rows and
+  files (``--no-share-frames``: a fresh engine and upload per sample);
 * J is computed on the GPU from the engine's mask tensor (``stcn_metrics_jf_counts``), only counts cross PCIe;
 * the 224x224 PNG states are encoded and written by host threads while the GPU propagates the next round.
 * two samples are in flight per GPU (host thread + HIP stream each, ``--lanes``): +9..17 % rounds/s;
@@ -245,24 +248,33 @@ class ClipDataset:
         return sample
 
 
-def prefetched(ds: "ClipDataset", indices, device: str = "cuda", timing: dict = None):
+def prefetched(ds: "ClipDataset", indices, device: str = "cuda", timing: dict = None, share_frames: bool = True):
     """Yield (i, sample) for i in indices with sample['rgb'] already on `device`.  The NEXT sample is decoded on a
     host thread (PIL releases the GIL) into pinned memory as BYTES, copied H2D and normalised on a side stream while the caller
-    propagates the current one (round 4: the host used to normalise in four NumPy passes over 200 MB per clip and upload fp32) - the reference decodes and uploads synchronously between samples (generate_fq_dataset.py:60-63)."""
+    propagates the current one (round 4: the host used to normalise in four NumPy passes over 200 MB per clip and upload fp32) - the reference decodes and uploads synchronously between samples (generate_fq_dataset.py:60-63).
+    ``share_frames``: a sample of the video the previous one belonged to (its next object) gets the device clip of that one - the same
+    tensor, neither uploaded nor normalised again."""
     from concurrent.futures import ThreadPoolExecutor
     on_gpu = torch.cuda.is_available() and str(device).startswith("cuda")
     side = torch.cuda.Stream() if on_gpu else None
+    last = {}                                                     # the clip of the loader's previous sample: video, rgb, _ready, _host
 
     def load(i):
         if not on_gpu:
             return dict(ds[i])
         sample = dict(ds.raw(i))
         host = sample.pop("rgb_u8")                               # pinned uint8 [T,H,W,3]: a quarter of the fp32 clip crosses PCIe
+        if share_frames and last.get("video") == sample["video"]:
+            sample.update(rgb=last["rgb"], _ready=last["_ready"], _host=last["_host"])
+            return sample
         with torch.cuda.stream(side):
             sample["rgb"] = ds.normalize_device(host.to(device, non_blocking=True))[None]      # normalised on the device, on the side stream
             ev = torch.cuda.Event()
             ev.record(side)
         sample["_ready"], sample["_host"] = ev, host              # keep the pinned buffer alive until the copy is done
+        last.clear()
+        if share_frames:
+            last.update(video=sample["video"], rgb=sample["rgb"], _ready=ev, _host=host)
         return sample
 
     indices = list(indices)
@@ -292,17 +304,66 @@ def lane_engine_options(lanes: int):
     return {"lookahead": 0} if lanes > 1 and "STCN_LOOKAHEAD" not in os.environ else None
 
 
-def run_lanes(root: str, imset: str, mine, lanes: int, work, device: str = "cuda", stats: dict = None, per_video: bool = False):
+class LaneCores:
+    """The InferenceCore of every lane thread, kept while the lane's consecutive samples belong to one video.  Per-object mode: one
+    annotation session per (video, object), as the reference runs them (interactions/eval.py:92-99) - but what the engine caches per
+    frame does not depend on the object, so the next object of the video gets the SAME core, re-targeted with
+    ``reset(keep_frame_features=True)``: no second engine, no second pass of the key encoder over the clip.  A new core is built only
+    when the video changes (the old one is dropped first: its device memory serves the new one).  ``share_frames=False``: a fresh core
+    per sample, the reference's protocol to the letter (A/B runs).  ``make(sample)`` constructs a core.
+    ``engines_created`` / ``key_frames_encoded`` count over all lanes (``done(core)`` adds a finished session's key-encoder frames)."""
+
+    def __init__(self, make, share_frames: bool = True):
+        import threading
+        self.make, self.share_frames = make, share_frames
+        self.local, self.lock = threading.local(), threading.Lock()
+        self.engines_created = self.key_frames_encoded = 0
+
+    def core_for(self, sample):
+        tl = self.local
+        if self.share_frames and getattr(tl, "core", None) is not None and tl.video == sample["video"]:
+            tl.core.reset(keep_frame_features=True)
+            return tl.core
+        tl.core = None
+        core = self.make(sample)
+        with self.lock:
+            self.engines_created += 1
+        if self.share_frames:
+            tl.core, tl.video = core, sample["video"]
+        return core
+
+    def done(self, core):
+        with self.lock:
+            self.key_frames_encoded += int(core.key_frames_encoded)
+
+    def release(self):
+        """The calling lane has no more samples: its core goes now, not when the last lane ends."""
+        self.local.core = None
+
+    def add_to(self, stats: dict):
+        for k_ in ("engines_created", "key_frames_encoded"):
+            stats[k_] = stats.get(k_, 0) + getattr(self, k_)
+
+
+def run_lanes(root: str, imset: str, mine, lanes: int, work, device: str = "cuda", stats: dict = None, per_video: bool = False,
+              share_frames: bool = True, lane_done=None):
     """Process the samples `mine` on `lanes` host threads, each with its own HIP stream, clip loader and prefetcher
     (samples are independent; two videos in flight fill each other's kernel tails, as bench.py's lanes do).
     work(i, sample) -> list of rows; returns all rows.  Chunks are contiguous so that the objects of one video stay
-    with one loader (per-video decode cache).  ``per_video``: the indices are those of ``ClipDataset(..., per_video=True)``."""
+    with one loader (per-video decode cache).  ``per_video``: the indices are those of ``ClipDataset(..., per_video=True)``.
+    ``share_frames`` (per-object samples): the chunks are cut between videos wherever there are at least as many videos as lanes, at about
+    equal frame counts (shard.chunk_bounds) - the objects of a video then meet one lane, one device clip and one engine (LaneCores) - and
+    the prefetcher uploads a clip once per video.  ``lane_done()``, if given, is called on every lane's thread after its last sample."""
     from concurrent.futures import ThreadPoolExecutor
     mine = list(mine)
     lanes = max(1, min(lanes, len(mine)))
     on_gpu = torch.cuda.is_available() and str(device).startswith("cuda")
     dev_index = torch.cuda.current_device() if on_gpu else None
-    bounds = [len(mine) * l // lanes for l in range(lanes + 1)]
+    if share_frames and not per_video and lanes > 1:
+        samples = ClipDataset(root, imset).samples
+        bounds = shard.chunk_bounds([samples[i][0] for i in mine], lanes, [samples[i][2] for i in mine])
+    else:
+        bounds = [len(mine) * l // lanes for l in range(lanes + 1)]
 
     def lane(l):
         ds = ClipDataset(root, imset, per_video=per_video)
@@ -316,13 +377,17 @@ def run_lanes(root: str, imset: str, mine, lanes: int, work, device: str = "cuda
         timing = {} if stats is not None else None
         t_lane = time.perf_counter()
         with ctx:
-            for i, sample in prefetched(ds, mine[bounds[l]:bounds[l + 1]], device, timing):
-                t_s = time.perf_counter()
-                rows += work(i, sample)
-                if timing is not None:
-                    timing["work_s"] = timing.get("work_s", 0.0) + time.perf_counter() - t_s
-            if on_gpu:
-                torch.cuda.current_stream().synchronize()
+            try:
+                for i, sample in prefetched(ds, mine[bounds[l]:bounds[l + 1]], device, timing, share_frames and not per_video):
+                    t_s = time.perf_counter()
+                    rows += work(i, sample)
+                    if timing is not None:
+                        timing["work_s"] = timing.get("work_s", 0.0) + time.perf_counter() - t_s
+                if on_gpu:
+                    torch.cuda.current_stream().synchronize()
+            finally:
+                if lane_done is not None:
+                    lane_done()
         if stats is not None:                                      # host-side account of the lane: where its wall time went
             timing["lane_s"] = time.perf_counter() - t_lane
             with _STATS_LOCK:
@@ -512,10 +577,14 @@ def save_rgb_frames(rgb: torch.Tensor, out_dir: str, pool=None):
 
 
 def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, save_masks: bool = True,
-        device: str = "cuda", lanes: int = 2, stats: dict = None):
+        device: str = "cuda", lanes: int = 2, stats: dict = None, share_frames: bool = True):
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
     (rows: sample id, round, selected frame, T, then T per-frame J values padded with NaN).
-    `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited) and `interactions` are added to it."""
+    `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited), `interactions`, `key_frames_encoded` (frames
+    that went through the key encoder) and `engines_created` are added to it.
+    `share_frames`: the sessions of a video's objects run one after the other on ONE engine that keeps the clip and its frame features
+    between them (LaneCores) - videos, not samples, are dealt to ranks and lanes.  Same rows, same files; False: a fresh engine and a
+    fresh upload per sample, samples dealt one by one."""
     import torch.distributed as dist
     from concurrent.futures import ThreadPoolExecutor
 
@@ -524,7 +593,12 @@ def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, sa
     world = dist.get_world_size() if dist.is_initialized() else 1
     ds = ClipDataset(root, imset)
     t_max = max(s[2] for s in ds.samples)
-    mine = sorted(shard.lpt_assign([s[2] for s in ds.samples], world)[rank])     # adjacent objects share a decode
+    frames = [s[2] for s in ds.samples]
+    if share_frames:
+        mine = sorted(shard.lpt_assign_grouped(frames, [s[0] for s in ds.samples], world)[rank])     # the objects of a video share an engine
+    else:
+        mine = sorted(shard.lpt_assign(frames, world)[rank])     # adjacent objects share a decode
+    cores = LaneCores(lambda sample: InferenceCore(prop_net, fuse_net, sample["rgb"], 1, engine_options=lane_engine_options(lanes)), share_frames)
     width = 4 + t_max
     writers = ThreadPoolExecutor(8) if save_masks else None           # zlib releases the GIL: the encoders really run beside the lanes
     pending = []
@@ -541,10 +615,11 @@ def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, sa
             if first:
                 pending.append(save_rgb_frames(sample["rgb"][0], os.path.join(out, "RGBFrames", "224", sample["video"]), writers))
         t_c = time.perf_counter()
-        proc = InferenceCore(prop_net, fuse_net, sample["rgb"], 1, engine_options=lane_engine_options(lanes))
+        proc = cores.core_for(sample)
         mine_stats = {"create_s": time.perf_counter() - t_c} if stats is not None else None
         t_c = time.perf_counter()
         states, gens = oracle_rounds(proc, sample, rounds, mine_stats)
+        cores.done(proc)
         if stats is not None:
             mine_stats["session_s"] = time.perf_counter() - t_c
             with rgb_lock:
@@ -563,7 +638,9 @@ def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, sa
             sid += 1
         return rows
 
-    rows = run_lanes(root, imset, mine, lanes, work, device, stats)
+    rows = run_lanes(root, imset, mine, lanes, work, device, stats, share_frames=share_frames, lane_done=cores.release)
+    if stats is not None:
+        cores.add_to(stats)
     t_p = time.perf_counter()
     for f in pending:
         f.result()                                         # surface write errors; all PNGs are on disk before the CSV
@@ -596,6 +673,8 @@ def main():
     ap.add_argument("--synthetic-weights", action="store_true", help="use the deterministic recipe (no checkpoints)")
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--lanes", type=int, default=2, help="videos in flight per GPU")
+    ap.add_argument("--no-share-frames", action="store_true", help="a fresh engine and a fresh upload of the clip for every object of a video "
+                    "(default: the sessions of a video's objects share one engine and its frame features; same output)")
     ap.add_argument("--top-k", type=int, default=50, help="rows of the memory bank each query reads, 1..50 (PropagationNetwork(top_k=...): 20 for STCN checkpoints, 50 for MiVOS)")
     ap.add_argument("--km", type=float, default=None, metavar="SIGMA", help="kernelized memory read: standard deviation (1/16-scale positions) of the Gaussian "
                     "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
@@ -613,7 +692,7 @@ def main():
     else:
         prop.load_state_dict(torch.load(a.prop_weights, map_location="cpu"))
         fuse.load_state_dict(torch.load(a.fusion_weights, map_location="cpu"))
-    rows = run(a.root, a.imset, a.out, prop.eval(), fuse.eval(), a.rounds, lanes=a.lanes)
+    rows = run(a.root, a.imset, a.out, prop.eval(), fuse.eval(), a.rounds, lanes=a.lanes, share_frames=not a.no_share_frames)
     if not dist.is_initialized() or dist.get_rank() == 0:
         print(f"{len(rows)} states -> {os.path.join(a.out, 'res_' + os.path.splitext(os.path.basename(a.imset))[0] + '.csv')}")
     if dist.is_initialized():

@@ -350,17 +350,27 @@ class InferenceCore:
         if cur != self._stream:
             cur.wait_stream(self._stream)
 
-    def reset(self):
+    def reset(self, keep_frame_features=False) -> int:
         """Forget all interactions / cached features (same clip): equivalent to constructing a new
-        InferenceCore on the same images, without re-allocating device memory."""
+        InferenceCore on the same images, without re-allocating device memory.
+
+        ``keep_frame_features=True``: the next session annotates ANOTHER OBJECT OF THE SAME CLIP.  Everything the engine caches per frame
+        at key-encoding time is a function of the frame and the model only, so it stays; interactions, memory, ``prob`` and ``masks`` are
+        forgotten as above.  Returns the number of frames whose features were kept - 0 for the plain form, for a clip longer than the key
+        cache (106 frames) and after a failed interaction, where the call is the plain reset.  The next session equals a fresh core's bit
+        for bit when it starts with the frame the earlier one started with (every driver session starts with frame 0); otherwise up to
+        the rounding of differently shaped launches (include/stcn_hip.h: STCN_RESET_KEEP_FRAMES)."""
+        kept = C.c_int32(0)
         with torch.cuda.device(self.device):
             cur = self._join_engine_stream()
             try:
-                _lib.check(_lib.lib().stcn_engine_reset(self._engine), "stcn_engine_reset")
+                _lib.check(_lib.lib().stcn_engine_reset_ex(self._engine, _lib.RESET_KEEP_FRAMES if keep_frame_features else 0, C.byref(kept)),
+                           "stcn_engine_reset_ex")
             finally:
                 self._leave_engine_stream(cur)
         self.interacted = set()
         self.np_masks = np.zeros((self.t, self.h, self.w), dtype=np.uint8)
+        return int(kept.value)
 
     def get_image_buffered(self, idx):
         lw, uw, lh, uh = self.pad
@@ -384,6 +394,14 @@ class InferenceCore:
         v = C.c_float()
         _lib.check(_lib.lib().stcn_model_get_km(self._model.handle, C.byref(v)), "stcn_model_get_km")
         return float(v.value) if v.value > 0 else None
+
+    @property
+    def key_frames_encoded(self) -> int:
+        """Frames that went through the key encoder since construction / the last ``reset()``: ``stats()["key_miss"]`` summed over the
+        interactions of the session so far (0 for a session that ran on kept frame features alone)."""
+        v = C.c_int64()
+        _lib.check(_lib.lib().stcn_get_key_frames(self._engine, C.byref(v)), "stcn_get_key_frames")
+        return int(v.value)
 
     def stats(self) -> dict:
         s = _lib.Stats()

@@ -5,7 +5,8 @@ Every dataset sample is one (video, object) with its own InferenceCore and no sh
 by ``--min-idx/--max-idx`` (eval_annotation_method.py:34-35).  Here: one process per GPU, a static
 longest-processing-time assignment of samples to ranks (work ~ frame count), NO collective inside
 propagation, and one end-of-run gather of fixed-width per-sample rows (RCCL over xGMI when the
-backend is "nccl"; "gloo" in the CPU tests)."""
+backend is "nccl"; "gloo" in the CPU tests).  The per-object sessions of a video share one engine and its
+frame features by default: the drivers then deal whole videos (``lpt_assign_grouped``, ``chunk_bounds``)."""
 from __future__ import annotations
 
 from typing import List, Sequence
@@ -67,6 +68,49 @@ def lpt_assign(costs: Sequence[float], world: int) -> List[List[int]]:
             out[b].remove(j); out[hi].append(j)
             load[b] -= costs[j]; load[hi] += costs[j]
     return [sorted(p, key=lambda i: (-costs[i], i)) for p in out]
+
+
+def _groups_in_order(groups: Sequence) -> List[List[int]]:
+    """The members of every group (a hashable key per sample), groups in the order of their first member, members in sample order."""
+    members: dict = {}
+    for i, g in enumerate(groups):
+        members.setdefault(g, []).append(i)
+    return list(members.values())
+
+
+def lpt_assign_grouped(costs: Sequence[float], groups: Sequence, world: int) -> List[List[int]]:
+    """``lpt_assign`` over GROUPS of samples: ``groups[i]`` is the key of sample i's group (the drivers: its video), a group is never
+    split, and its cost is the sum of its members' (the objects of a video cost its frames each: frames x objects).  The per-object
+    sessions of a video run on one engine that keeps the frame features between them (InferenceCore.reset(keep_frame_features=True)), so
+    they have to land on one rank.  Deterministic, every sample exactly once; a rank lists its groups in ``lpt_assign``'s order and the
+    members of a group in sample order - with one member per group the result IS ``lpt_assign(costs, world)``."""
+    if len(groups) != len(costs):
+        raise ValueError(f"{len(costs)} costs for {len(groups)} group keys")
+    members = _groups_in_order(groups)
+    parts = lpt_assign([sum(costs[i] for i in m) for m in members], world)
+    return [[i for g in part for i in members[g]] for part in parts]
+
+
+def chunk_bounds(groups: Sequence, chunks: int, costs: Sequence[float] = None) -> List[int]:
+    """Cut a sequence of samples into ``chunks`` contiguous pieces of about equal cost (``costs``; default: one per sample): the
+    ``chunks + 1`` bounds, first 0, last ``len(groups)``.  ``groups[i]`` is the group key of sample i, the samples of a group adjacent
+    (the drivers: the objects of a video): when there are at least as many groups as chunks every cut falls between two groups and no
+    piece is empty; with fewer groups than chunks the pieces hold equal numbers of samples and groups are split."""
+    n = len(groups)
+    edges = [0] + [i for i in range(1, n) if groups[i] != groups[i - 1]] + [n]      # where a cut splits no group
+    if chunks < 1 or len(edges) - 1 < chunks:
+        return [n * c // max(chunks, 1) for c in range(max(chunks, 1) + 1)]
+    acc = [0.0]
+    for i in range(n):
+        acc.append(acc[-1] + (costs[i] if costs is not None else 1.0))
+    bounds, lo = [0], 0                                   # lo: index into edges of the last cut
+    for c in range(1, chunks):
+        want = acc[-1] * c / chunks
+        # the edge nearest to the ideal cut (ties: the earlier one) that leaves a group for this piece and one for every later piece
+        e = min(range(lo + 1, len(edges) - (chunks - c)), key=lambda j: (abs(acc[edges[j]] - want), j))
+        bounds.append(edges[e])
+        lo = e
+    return bounds + [n]
 
 
 def gather_rows(rows: np.ndarray, width: int, device=None) -> np.ndarray:

@@ -123,6 +123,21 @@ int stcn_engine_get_opts(const stcn_engine *e, stcn_engine_opts *out);
  * constructs a new InferenceCore per sample, interactions/eval.py:99.) */
 int stcn_engine_reset(stcn_engine *e);
 
+/* stcn_engine_reset with flags; stcn_engine_reset(e) = stcn_engine_reset_ex(e, 0, NULL).
+ *   STCN_RESET_KEEP_FRAMES  the next session is for ANOTHER OBJECT OF THE SAME CLIP: interactions, certain memory, bank contents, statistics
+ *       and a failed state are forgotten and prob / masks re-initialised as above, but the packed clip and the occupied key-cache slots
+ *       stay.  What a slot holds (key, |key|^2, the 1/16, 1/8 and 1/4-scale encoder features, the frame-only parts of the value encoder) is
+ *       a function of the frame and the model only, so the next session encodes no key for a kept frame (stcn_stats.key_miss counts only
+ *       frames that were not kept).  Its results are bit-identical to a fresh engine's wherever that engine would have key-encoded the
+ *       frames in the same batches - every session starting with the same frame is such a case; otherwise the slot order and the batch
+ *       shapes of the key encoder and the decoder differ, and results agree up to the rounding of differently shaped launches.
+ *       The features are dropped (the call then behaves as with flags = 0) when the engine was in a failed state - the failed interaction may
+ *       have left slots half-written - and when the clip is longer than the key cache (T > 106 frames: recycled slots have no stable content).
+ *   kept_frames (may be NULL) receives the number of frames whose features were kept, 0 when none were.
+ * Both forms drain the engine's side streams first.  Unknown flag bits and a null engine return STCN_E_INVALID before any device call. */
+#define STCN_RESET_KEEP_FRAMES 1u
+int stcn_engine_reset_ex(stcn_engine *e, uint32_t flags, int32_t *kept_frames);
+
 /* Deep copy of all engine state (certain memory, key cache, interaction set).  The clone writes to
  * the caller-provided prob/masks buffers, which the caller must have filled with a copy of the
  * source's.  Replaces: copy.deepcopy(processor) (interactions/policies.py:103-104). */
@@ -150,6 +165,9 @@ typedef struct {
     int32_t frames, key_miss, value_enc, fused, bank_fwd, bank_bwd;
 } stcn_stats;
 int stcn_get_stats(const stcn_engine *e, stcn_stats *out);
+/* key_miss summed over the interactions since stcn_engine_create / the last reset (either form): the frames the session so far sent
+ * through the key encoder - 0 for a session that ran on kept frame features alone.  A clone starts at its source's count. */
+int stcn_get_key_frames(const stcn_engine *e, int64_t *out);
 
 /* Algorithmic work of the last interact() in FLOP (2 x MAC of every conv / GEMM issued). */
 int stcn_get_flops(const stcn_engine *e, double *flops);
