@@ -65,6 +65,9 @@ PROTOTYPES = {
     "stcn_engine_reset_ex": (_I, [_P, C.c_uint32, C.POINTER(C.c_int32)]),
     "stcn_engine_clone": (_I, [_P, _P, _P, _P, C.POINTER(_P)]),
     "stcn_interact": (_I, [_P, _P, _I, _I, _I]),
+    "stcn_engine_set_undo": (_I, [_P, _I]),
+    "stcn_engine_undo": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "stcn_engine_get_undo": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "stcn_get_stats": (_I, [_P, C.POINTER(Stats)]),
     "stcn_get_key_frames": (_I, [_P, C.POINTER(C.c_int64)]),
     "stcn_get_flops": (_I, [_P, C.POINTER(_D)]),
@@ -95,6 +98,7 @@ PROTOTYPES = {
     "stcn_metrics_jf_counts": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "stcn_metrics_j_counts": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "stcn_metrics_round": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P]),
+    "stcn_metrics_trial": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P]),
     "stcn_metrics_objects_scratch": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int64)]),
     "stcn_metrics_objects_jf_counts": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "stcn_metrics_objects_j_counts": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),

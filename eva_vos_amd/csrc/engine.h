@@ -246,5 +246,15 @@ struct stcn_engine {
     stcn_stats stats{};
     int64_t key_frames = 0;              // frames that went through the key encoder since creation / the last reset (stcn_get_key_frames)
     std::string failed;                  // non-empty: a failed interaction left prob / masks half-written (see stcn_interact)
+    // undo journal (stcn_engine_set_undo): the last undo_depth interactions, oldest first.  An entry holds what its interaction was about
+    // to overwrite - frames [f0, f0 + n) of the k + 1 prob rows, then the same frames of masks, in ONE pool buffer sized to that span - and the
+    // host bookkeeping to put back.  A dropped entry's buffer is RETIRED: copies out of / into it may still be in flight on the engine's
+    // stream, so it is reused by this engine's next save (same stream: ordered) or handed to the pool once undo_ev, recorded behind the
+    // latest retirement, has fired.  Depth 0: all of this stays empty and nothing is allocated, recorded or enqueued.
+    struct UndoEntry { int idx, f0, n, n_certain0; bool was_interacted; void *buf; size_t bytes; };
+    int undo_depth = 0;
+    std::deque<UndoEntry> journal;
+    std::vector<std::pair<void *, size_t>> undo_retired;
+    hipEvent_t undo_ev = nullptr;
     std::vector<void *> allocs;
 };

@@ -501,6 +501,25 @@ int stcn_metrics_round(void *stream, const uint8_t *masks_dev, int nh, int nw, i
                          no_object, gen_dev, scratch_dev, counts_dev, nullptr, quality_dev, select_dev);
 }
 
+int stcn_metrics_trial(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev, const uint8_t *annotated_dev,
+                       const uint8_t *noobj_dev, int candidate, int T, int H, int W, int t0, int t1, int j_only, double no_object,
+                       const int32_t *counts_dev, uint8_t *span_gen_dev, uint8_t *scratch_dev, int32_t *span_counts_dev, double *quality_dev) {
+    const char *who = "stcn_metrics_trial";
+    const void *unused = who;
+    if (!metric_args_ok(who, false, 0, T, H, W, 2, {masks_dev, gt_dev, annotated_dev, noobj_dev, counts_dev, span_gen_dev, span_counts_dev, quality_dev,
+                                                    j_only ? unused : scratch_dev}))
+        return STCN_E_INVALID;
+    if (lh < 0 || lw < 0 || lh + H > nh || lw + W > nw) { set_error("%s: the %d x %d crop at (%d, %d) leaves the %d x %d tensor", who, H, W, lh, lw, nh, nw); return STCN_E_INVALID; }
+    if (t0 < 0 || t1 > T || t0 > t1) { set_error("%s: frames [%d, %d) are not a range inside [0, %d)", who, t0, t1, T); return STCN_E_INVALID; }
+    if (candidate < 0 || candidate >= T) { set_error("%s: candidate frame %d outside [0, %d)", who, candidate, T); return STCN_E_INVALID; }
+    const size_t hw = (size_t)H * W;
+    trial_score_launch(masks_dev + (size_t)t0 * nh * nw, nh, nw, lh, lw, gt_dev + t0 * hw, annotated_dev + t0, noobj_dev,
+                       candidate >= t0 && candidate < t1 ? candidate - t0 : -1, T, H, W, t0, t1, j_only ? -1 : bound_radius(H, W), no_object, counts_dev,
+                       span_gen_dev, scratch_dev, span_counts_dev, quality_dev, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
 int stcn_metrics_objects_round(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev,
                                const uint8_t *annotated_dev, const uint8_t *present_dev, int k, int T, int H, int W, int t0, int t1, int j_only,
                                double no_object, uint8_t *gen_dev, void *scratch_dev, int32_t *counts_dev, double *object_quality_dev,

@@ -303,6 +303,11 @@ void label_counts_launch(const uint8_t *gt, const uint8_t *pred, int k, int Tn, 
 void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *flags, int k,
                         int Tn, int H, int W, int radius, double no_object, uint8_t *gen, void *scratch, int *counts, int T_all,
                         double *object_quality, double *quality, int *select, hipStream_t s, int t0);
+// A trial round of a binary session (stcn_metrics_trial): frames [t0, t1) composed - frame t0 + also counting as annotated, -1: none - and
+// counted into span_gen / bmap / span_counts, then quality [T_all] from span_counts inside the span and the const base counts outside.
+void trial_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *noobj, int also,
+                        int T_all, int H, int W, int t0, int t1, int radius, double no_object, const int *base, uint8_t *span_gen, uint8_t *bmap,
+                        int *span_counts, double *quality, hipStream_t s);
 
 // pure fp32-MFMA load (no memory traffic): launches `grid` workgroups of 12 waves x iters x 12 MFMAs, returns the FLOP of the launch
 double mfma_probe_launch(float *out, int grid, int iters, hipStream_t s);

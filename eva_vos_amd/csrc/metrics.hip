@@ -276,17 +276,18 @@ void label_counts_launch(const uint8_t *gt, const uint8_t *pred, int k, int Tn, 
 // ---- one annotation round on the device (round 6): compose -> counts -> quality + selection ------------------------------------------
 // gen[t] = the engine's mask of frame t (cropped out of the padded [T][nh][nw] tensor), or the ground truth where the frame is annotated
 // (interactions/eval.py:57-60: annotated frames count with their GT mask).  gen is what util/fq_dataset.py:64-84 saves as a state.
-// Binary masks: non-zero = object; LABELS: label maps of k objects.
+// Binary masks: non-zero = object; LABELS: label maps of k objects.  `also`: one more frame (of the T composed) that counts as annotated
+// whatever its flag says - the candidate of a trial round, whose flags are the caller's and stay untouched; -1: none.
 template <bool LABELS>
 __global__ __launch_bounds__(256) void round_compose_kernel(const uint8_t *__restrict__ masks, int nh, int nw, int lh, int lw,
                                                             const uint8_t *__restrict__ gt, const uint8_t *__restrict__ annotated, int k, int T, int H,
-                                                            int W, uint8_t *__restrict__ gen) {
+                                                            int W, uint8_t *__restrict__ gen, int also) {
     const long hw = (long)H * W, n = T * hw;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const int t = (int)(i / hw);
         const int rem = (int)(i - t * hw);
         const int y = rem / W, x = rem - y * W;
-        const uint8_t v = annotated[t] ? gt[i] : masks[((long)t * nh + y + lh) * nw + x + lw];
+        const uint8_t v = annotated[t] || t == also ? gt[i] : masks[((long)t * nh + y + lh) * nw + x + lw];
         gen[i] = LABELS ? (uint8_t)label_of(v, k) : (uint8_t)(v != 0);
     }
 }
@@ -368,11 +369,41 @@ void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, co
     const long n = (long)Tn * H * W;
     const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(k ? round_compose_kernel<true> : round_compose_kernel<false>, dim3(blocks), dim3(256), 0, s, masks, nh, nw, lh, lw, gt, annotated, k,
-                       Tn, H, W, gen);
+                       Tn, H, W, gen, -1);
     if (k) label_counts_launch(gt, gen, k, Tn, H, W, radius, scratch, counts, T_all, s);
     else jf_counts_launch(gt, gen, Tn, H, W, radius, (uint8_t *)scratch, counts, s);
     hipLaunchKernelGGL(round_quality_kernel, dim3(1), dim3(256), 0, s, counts - (long)t0 * 6, flags, k ? 0 : 1, k ? k : 1, T_all, radius < 0 ? 1 : 0,
                        no_object, k ? object_quality : nullptr, quality, select);
+}
+
+// ---- a trial round: the quality row of "annotate `candidate` next", beside the caller's rounds ------------------------------------------
+// quality[t] for all T frames from TWO count arrays: span [(t1 - t0)][6] - counted just now over the frames the trial can have changed -
+// for t in [t0, t1), base [T][6] - the caller's last round, read only - for every other frame; NO_OBJECT for flagged frames.  The value is
+// quality_of, which is what round_quality_kernel writes for one object (its mean over one object is exact, see there).
+__global__ __launch_bounds__(256) void trial_quality_kernel(const int *__restrict__ base, const int *__restrict__ span, int t0, int t1,
+                                                            const uint8_t *__restrict__ noobj, int T, int j_only, double no_object,
+                                                            double *__restrict__ quality) {
+    for (int t = blockIdx.x * 256 + threadIdx.x; t < T; t += gridDim.x * 256) {
+        const int *c = t >= t0 && t < t1 ? span + (long)(t - t0) * 6 : base + (long)t * 6;
+        quality[t] = noobj[t] ? no_object : quality_of(c, j_only);
+    }
+}
+
+// Compose + count frames [t0, t1) into the caller's scratch (masks / gt / annotated point at frame t0, as in round_score_launch; noobj and
+// base are whole-clip arrays), then one quality row.  `also`: the candidate's index inside the span, -1 when it lies outside.  Writes
+// span_gen, bmap, span_counts and quality, nothing else.
+void trial_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *noobj, int also,
+                        int T_all, int H, int W, int t0, int t1, int radius, double no_object, const int *base, uint8_t *span_gen, uint8_t *bmap,
+                        int *span_counts, double *quality, hipStream_t s) {
+    const int Tn = t1 - t0;
+    if (Tn > 0) {
+        const long n = (long)Tn * H * W;
+        const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(round_compose_kernel<false>, dim3(blocks), dim3(256), 0, s, masks, nh, nw, lh, lw, gt, annotated, 0, Tn, H, W, span_gen, also);
+        jf_counts_launch(gt, span_gen, Tn, H, W, radius, bmap, span_counts, s);
+    }
+    hipLaunchKernelGGL(trial_quality_kernel, dim3((T_all + 255) / 256), dim3(256), 0, s, base, span_counts, t0, t1, noobj, T_all, radius < 0 ? 1 : 0,
+                       no_object, quality);
 }
 
 }  // namespace stcn

@@ -44,9 +44,13 @@ MAX_OBJECTS = 32                                              # STCN_MAX_OBJECTS
 MASK_SECONDS, SKIP_SECONDS = 80, 3            # annotation cost model of interactions/mask.py:33-36
 
 
-def _upper_bound_frame(processor, gt, gt_thw, frames, metric):
+KEY_CACHE_FRAMES = 106                                       # the engine's key cache: a clip of at most this many frames never recycles a slot
+
+
+def _upper_bound_frame(processor, gt, gt_thw, frames, metric, stats=None):
     """get_frame_upper_bound (interactions/policies.py:90-117): try every remaining frame on a deep copy of the
-    processor and keep the one with the best mean metric (last maximum wins, as the reference's ``>=``)."""
+    processor and keep the one with the best mean metric (last maximum wins, as the reference's ``>=``).  The path of clips longer than
+    the key cache: their cache recycles, a trial on the session's own engine would change the shapes of its later launches."""
     best, best_f = -np.inf, -1
     for f in range(gt.shape[0]):
         if f in frames:
@@ -57,10 +61,38 @@ def _upper_bound_frame(processor, gt, gt_thw, frames, metric):
         if mu >= best:
             best, best_f = mu, f
         del p
+        if stats is not None:
+            stats["trial_interactions"] = stats.get("trial_interactions", 0) + 1
+            stats["engine_clones"] = stats.get("engine_clones", 0) + 1
     return best_f
 
 
-def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and_f", qnet=None, rng=None, multi_object: bool = False):
+def _upper_bound_frame_in_place(processor, scorer, gt, frames, stats=None):
+    """The same selection without a second engine, for clips that fit the key cache: every remaining frame is tried ON the session's engine
+    - ``interact``, ``RoundScorer.score_trial``, ``undo`` (undo depth 1) - all candidates enqueued back to back; the host waits once, for
+    the table of trial rows.  From the second interaction of such a clip on every key is cached, so a trial that is taken back leaves the
+    engine's later results byte-identical (include/stcn_hip.h), and a trial row is what ``frame_quality`` returns for the copy, to the bit:
+    with the mean over the frames with an object and the ``>=`` below - the expressions of ``_upper_bound_frame`` - the selection is the
+    same by construction."""
+    candidates = [f for f in range(gt.shape[0]) if f not in frames]
+    for row, f in enumerate(candidates):
+        processor.interact(gt[f][None], f, download=False)
+        scorer.score_trial(processor, frames, f, row)
+        processor.undo(download=False)
+    q = scorer.trial_rows(len(candidates))
+    empty = scorer.empty_host
+    best, best_f = -np.inf, -1
+    for row, f in enumerate(candidates):
+        mu = float(np.mean(q[row][~empty])) if (~empty).any() else float("nan")
+        if mu >= best:
+            best, best_f = mu, f
+    if stats is not None:
+        stats["trial_interactions"] = stats.get("trial_interactions", 0) + len(candidates)
+    return best_f
+
+
+def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and_f", qnet=None, rng=None, multi_object: bool = False,
+               stats: dict = None):
     """One sample through ``rounds`` annotation rounds.  Returns dict(mu_metrics, annotation_times, frames,
     round_metrics, propagated_frames): mu_metrics[r] / annotation_times[r] as the reference returns them; frames = annotated frames in
     order; round_metrics[r] = per-frame quality after round r; propagated_frames = frames the engine really visited (rounds >= 2 only
@@ -69,7 +101,11 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
     (``InferenceCore(..., num_objects=k)``): the annotation of frame f is the (k+1)-channel one-hot of its label map, background first, through
     the reference's ``scribble=True`` path; a round is scored by the k-object evaluation on the device, the values above are those of the FRAME
     quality (the mean over the objects present in the frame; a frame is valid while any object is present in it), and ``object_metrics[r]``
-    [k,T] / ``present`` [k,T] are added."""
+    [k,T] / ``present`` [k,T] are added.
+    ``upper_bound_mask`` tries its candidates on the session's own engine and takes them back (``_upper_bound_frame_in_place``) when the clip
+    fits the key cache, on deep copies of the engine (``_upper_bound_frame``) when it does not: decided by the clip length alone.
+    ``stats`` (optional dict): ``propagated_frames`` and ``interactions`` of the session's own rounds are added to it, and for the upper
+    bound ``trial_interactions`` (candidates tried) and ``engine_clones`` (deep copies made)."""
     assert policy in POLICIES, policy
     if multi_object and policy not in MULTI_OBJECT_POLICIES:
         raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
@@ -103,16 +139,29 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
         if policy == "qnet_mask":
             from .qnet import qnet_frame_selection
             return qnet_frame_selection(qnet, images, gen.float(), frames)
-        return _upper_bound_frame(processor, gt, gt_thw, frames, metric)
+        if in_place:
+            return _upper_bound_frame_in_place(processor, scorer, gt, frames, stats)
+        return _upper_bound_frame(processor, gt, gt_thw, frames, metric, stats)
 
-    stats = {}
-    frames, gens = annotation_session(processor, scorer, T, rounds, annotate, choose, keep_gen=policy == "qnet_mask", stats=stats)
+    stats = {} if stats is None else stats
+    seen = stats.get("propagated_frames", 0)
+    in_place = policy == "upper_bound_mask" and T <= KEY_CACHE_FRAMES
+    if policy == "upper_bound_mask":
+        stats.setdefault("trial_interactions", 0), stats.setdefault("engine_clones", 0)
+    depth = processor.undo_state()["depth"] if in_place else 0
+    if in_place:
+        processor.set_undo_depth(max(depth, 1))
+    try:
+        frames, gens = annotation_session(processor, scorer, T, rounds, annotate, choose, keep_gen=policy == "qnet_mask", stats=stats)
+    finally:
+        if in_place:
+            processor.set_undo_depth(depth)                        # the core goes back to its lane as it came
     empty, scored = scorer.empty_host, len(gens)
     times = [MASK_SECONDS] + [SKIP_SECONDS if empty[f] else MASK_SECONDS for f in frames[1:]]
     q = scorer.qualities()
     per_round = [q[i].copy() for i in range(scored)]
     mus = [float(np.mean(row[~empty])) if (~empty).any() else float("nan") for row in per_round]
-    res = dict(mu_metrics=mus, annotation_times=times[:-1], frames=frames, round_metrics=per_round, propagated_frames=stats.get("propagated_frames", 0))
+    res = dict(mu_metrics=mus, annotation_times=times[:-1], frames=frames, round_metrics=per_round, propagated_frames=stats.get("propagated_frames", 0) - seen)
     if multi_object:
         oq = scorer.object_qualities()
         res.update(object_metrics=[oq[i].copy() for i in range(scored)], present=scorer.present_host)
@@ -125,7 +174,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
     (rows: sample id, round, mu_metric, annotation_time, annotated frame, T, then T per-frame values, NaN-padded).
     `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited), `interactions`, `key_frames_encoded` (frames that
-    went through the key encoder) and `engines_created` are added to it.
+    went through the key encoder) and `engines_created` are added to it, for `upper_bound_mask` also `trial_interactions` and `engine_clones`.
     `share_frames` (per-object mode; the protocol and the rows stay the reference's): the sessions of a video's objects run one after the
     other on ONE engine that keeps the clip and its frame features between them (fq_driver.LaneCores) - videos, not samples, are dealt to
     ranks and lanes.  False: a fresh engine and a fresh upload per sample, samples dealt one by one.
@@ -160,7 +209,8 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         t_c = time.perf_counter()
         proc = cores.core_for(sample)
         t_s = time.perf_counter()
-        res = run_policy(policy, proc, sample, rounds, metric, qnet, random.Random(seed * 100003 + i), multi_object=multi_object)
+        session = {}
+        res = run_policy(policy, proc, sample, rounds, metric, qnet, random.Random(seed * 100003 + i), multi_object=multi_object, stats=session)
         cores.done(proc)
         if stats is not None:
             with stats_lock:
@@ -168,6 +218,9 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
                 stats["session_s"] = stats.get("session_s", 0.0) + time.perf_counter() - t_s
                 stats["propagated_frames"] = stats.get("propagated_frames", 0) + res["propagated_frames"]
                 stats["interactions"] = stats.get("interactions", 0) + len(res["mu_metrics"])
+                for n in ("trial_interactions", "engine_clones"):
+                    if n in session:
+                        stats[n] = stats.get(n, 0) + session[n]
         if multi_object:
             for o, sid in enumerate(sample["object_ids"]):
                 here = res["present"][o]

@@ -308,8 +308,11 @@ class InferenceCore:
                 self._leave_engine_stream(cur)
             self.last_enqueue_s = time.perf_counter() - t_enq      # host time of the enqueue-only C call (no sync inside): what a lane's thread costs the host
             self.interacted.add(idx)
-            if not download:
-                return None
+            return self._download_masks() if download else None
+
+    def _download_masks(self):
+        """The engine's masks, unpadded, as a fresh np.uint8 [t,h,w] (also kept as ``np_masks``); waits for the engine's stream."""
+        with torch.cuda.device(self.device):
             lw, uw, lh, uh = self.pad
             out = self.masks[:, 0, lh:self.nh - uh, lw:self.nw - uw]
             self.np_masks = None                                    # the previous result no longer counts against this core's budget (unless the caller kept it)
@@ -333,6 +336,35 @@ class InferenceCore:
                     _PAGEABLE_DOWNLOADS[0] += 1
                 self.np_masks = out.cpu().numpy().astype(np.uint8, copy=False)     # D2H sync, as the reference's .cpu(); a fresh array per call
         return self.np_masks
+
+    # ------------------------------------------------------------------------------------------ undo (not in the reference)
+    def set_undo_depth(self, n: int) -> None:
+        """Keep the last ``n`` interactions undoable (``stcn_engine_set_undo``); 0 - the default - switches the journal off, and the core is
+        then what it is without it.  With ``n >= 1`` every ``interact()`` first saves the frames it is about to overwrite (device memory
+        sized to that span, ``undo_state()["bytes"]``); lowering ``n`` drops the oldest entries."""
+        _lib.check(_lib.lib().stcn_engine_set_undo(self._engine, int(n)), "stcn_engine_set_undo")
+
+    def undo(self, download=True):
+        """Take the last interaction back in place: ``prob``, ``masks``, the certain memory and the interacted frames are what they were
+        before it, byte for byte (include/stcn_hip.h states what is deliberately left as it is, and when later results are bit-identical
+        to those of a core that never ran the undone call).  Returns the masks as ``interact`` does - np.uint8 [t,h,w] - or None with
+        ``download=False``.  Raises RuntimeError when there is nothing to undo (depth 0, an empty journal) or after a failed interaction."""
+        idx, still = C.c_int32(-1), C.c_int32(0)
+        with torch.cuda.device(self.device):
+            cur = self._join_engine_stream()
+            try:
+                _lib.check(_lib.lib().stcn_engine_undo(self._engine, C.byref(idx), C.byref(still)), "stcn_engine_undo")
+            finally:
+                self._leave_engine_stream(cur)
+            if not still.value:
+                self.interacted.discard(int(idx.value))
+            return self._download_masks() if download else None
+
+    def undo_state(self) -> dict:
+        """``depth`` as set, ``entries`` held now and the device ``bytes`` of their buffers (``stcn_engine_get_undo``)."""
+        d, n, b = C.c_int32(), C.c_int32(), C.c_int64()
+        _lib.check(_lib.lib().stcn_engine_get_undo(self._engine, C.byref(d), C.byref(n), C.byref(b)), "stcn_engine_get_undo")
+        return dict(depth=int(d.value), entries=int(n.value), bytes=int(b.value))
 
     # The engine enqueues on the HIP stream that was current when the core was constructed.  Normal PyTorch stream
     # semantics are kept for callers that use the core under ANOTHER current stream: the engine stream first waits for the

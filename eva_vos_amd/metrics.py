@@ -258,6 +258,7 @@ class RoundScorer:
         self.select_host = torch.empty((max_rounds,), dtype=torch.int32).pin_memory()
         self.event = torch.cuda.Event(blocking=True)
         self.rounds = 0
+        self._scored = frozenset()
 
     def score(self, processor, annotated_frames, keep_gen: bool = True, incremental: bool = True):
         """Enqueue the evaluation of the round just propagated by ``processor`` and return (selected frame, gen): gen = uint8 [T,H,W] on the
@@ -299,7 +300,58 @@ class RoundScorer:
             self.event.record()
             self.event.synchronize()                                  # blocking wait: the lane's host thread sleeps until the round is done
         self.rounds = r + 1
+        self._scored = frozenset(frames)                             # what `annotated` and `counts` on the device describe: score_trial builds on it
         return int(self.select_host[r]), gen
+
+    def score_trial(self, processor, annotated_frames, candidate: int, row: int) -> None:
+        """Enqueue the evaluation of a TRIAL (``stcn_metrics_trial``; binary sessions): ``processor`` has just tried ``interact`` on frame
+        ``candidate`` on top of the round scored last, whose annotated frames are ``annotated_frames``, and will take it back
+        (``InferenceCore.undo``).  Row ``row`` of the trial table receives the per-frame quality a real round with that annotation would get,
+        to the bit: the frames the trial can have changed - between the annotated neighbours of ``candidate`` - are composed and counted into
+        scratch, the others take the counts of the last round.  No host wait; ``rounds``, ``counts``, the evaluated masks and ``annotated``
+        stay what they were, so the next ``score()`` is that of a scorer that ran no trial.  The table holds T rows (``max_trials``)."""
+        import torch
+
+        from . import _lib
+        if self.k is not None:
+            raise RuntimeError("RoundScorer.score_trial: trials are scored for one-object (binary) sessions only")
+        frames, cand, row = frozenset(int(f) for f in annotated_frames), int(candidate), int(row)
+        if self.rounds == 0 or frames != self._scored:
+            raise RuntimeError("RoundScorer.score_trial: a trial builds on the round scored last; annotated_frames are not that round's")
+        if not 0 <= cand < self.T:
+            raise ValueError(f"RoundScorer.score_trial: candidate frame {cand} outside [0, {self.T})")
+        with torch.cuda.device(self.dev):
+            if getattr(self, "trial_quality", None) is None:
+                self.max_trials = self.T
+                self.trial_quality = torch.empty((self.max_trials, self.T), dtype=torch.float64, device=self.dev)
+                self.trial_host = torch.empty((self.max_trials, self.T), dtype=torch.float64).pin_memory()
+                self._trial_gen = torch.empty((self.T * self.H * self.W,), dtype=torch.uint8, device=self.dev)
+                self._trial_counts = torch.empty((self.T, 6), dtype=torch.int32, device=self.dev)
+            if not 0 <= row < self.max_trials:
+                raise RuntimeError(f"RoundScorer.score_trial: row {row} outside the trial table of {self.max_trials} rows")
+            t0 = max([f for f in frames if f < cand] + [-1]) + 1
+            t1 = min([f for f in frames if f > cand] + [self.T])
+            lw, uw, lh, uh = processor.pad
+            # the boundary map is scratch of a single call in score() too: trials share it
+            _lib.check(_lib.lib().stcn_metrics_trial(
+                _stream(), _ptr(processor.masks), processor.nh, processor.nw, lh, lw, _ptr(self.gt), _ptr(self.annotated), _ptr(self.noobj), cand,
+                self.T, self.H, self.W, t0, t1, 1 if self.metric == "j" else 0, self.no_object, _ptr(self.counts), _ptr(self._trial_gen),
+                _ptr(self.scratch), _ptr(self._trial_counts), _ptr(self.trial_quality[row])), "stcn_metrics_trial")
+
+    def trial_rows(self, n: int):
+        """float64 [n, T]: rows 0 .. n - 1 of the trial table - ONE device-to-host copy into pinned memory and one blocking-event wait (the
+        host thread sleeps until every trial enqueued so far is done)."""
+        import torch
+        n = int(n)
+        if n < 0 or n > getattr(self, "max_trials", 0):
+            raise RuntimeError(f"RoundScorer.trial_rows: {n} rows asked of a trial table of {getattr(self, 'max_trials', 0)}")
+        if n == 0:
+            return np.zeros((0, self.T), np.float64)
+        with torch.cuda.device(self.dev):
+            self.trial_host[:n].copy_(self.trial_quality[:n], non_blocking=True)
+            self.event.record()
+            self.event.synchronize()
+        return self.trial_host[:n].numpy().copy()
 
     def qualities(self):
         """float64 [rounds, T]: the per-frame quality of every round scored so far (one D2H copy)."""

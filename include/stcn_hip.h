@@ -169,6 +169,45 @@ int stcn_get_stats(const stcn_engine *e, stcn_stats *out);
  * through the key encoder - 0 for a session that ran on kept frame features alone.  A clone starts at its source's count. */
 int stcn_get_key_frames(const stcn_engine *e, int64_t *out);
 
+/* ---- undo: take the last interaction(s) back in place -----------------------------------------------------------------------
+ * For callers that TRY an annotation and take it back: the upper-bound policy tries every remaining frame in every round
+ * (get_frame_upper_bound, interactions/policies.py:90-117, on a copy.deepcopy of the processor per candidate), an interactive front end
+ * (the GUI the reference's InferenceCore docstring names) lets its user step back.  Neither needs a second engine: an interaction at idx
+ * rewrites prob / masks only in the frames strictly between the interacted neighbours of idx, appends one certain-memory slot and may
+ * add idx to the set of interacted frames.
+ *
+ * stcn_engine_set_undo keeps the last `depth` interactions undoable; 0 - the default - switches the journal off: the engine then allocates
+ * nothing, enqueues nothing and records nothing for it, every other call is what it is without this section, bit for bit.  Lowering the
+ * depth drops the oldest entries.  A negative depth or a null engine returns STCN_E_INVALID before any device call.
+ * With depth >= 1 stcn_interact first saves the frames it is about to overwrite - the k + 1 rows of prob and the masks of those frames -
+ * into a buffer from the engine-buffer pool sized to that span (stcn_engine_get_undo reports the bytes), after its up-front reservation
+ * has succeeded and before its first mutation; the copies are enqueued on the engine's stream, with no synchronisation.  A call that
+ * fails in that reservation (or for lack of memory for the journal itself) adds no entry; a failure INSIDE an interaction empties the
+ * journal with the rest of the failed state.  The buffer of a dropped entry (depth overflow, reset, a consumed undo) returns to the pool
+ * once the stream is past its last use; the engine's next save may take it before that.
+ *
+ * stcn_engine_undo takes the newest entry back (enqueue only): restores the saved frames, pops the certain slot, and removes the frame
+ * from the interacted set unless it was in it before.  idx_out / still_interacted_out (each may be NULL) receive the frame of the undone
+ * interaction and whether it is still interacted (1: the undone call was a re-annotation).  An empty journal and an engine in a failed
+ * state return STCN_E_STATE and touch nothing: the rule "stcn_engine_reset() after a failure" stands, undo does not recover from one.
+ *
+ * NOT restored, on purpose:
+ *   - key-cache slots filled by the undone interaction: plain caches, a function of the frame and the model only (the lazily written
+ *     frame parts of the value encoder included: they are computed one frame at a time, the same bytes whoever writes them);
+ *   - the engine's pos / neg / padded-mask scratch: every interaction rewrites it before reading it;
+ *   - stcn_stats, stcn_get_key_frames, the profiling counters: they keep describing the work that was done.
+ * GUARANTEE.  After stcn_engine_undo the engine's prob, masks, certain memory and interacted set are byte-identical to what they were
+ * before the undone call.  If the undone interaction encoded no key (stcn_stats.key_miss == 0 - from the second interaction of a clip of
+ * at most 106 frames on, every key is cached), every later result is byte-identical to that of an engine that never ran it.  Otherwise the
+ * cache holds other slots than it would, later key-encoder and decoder passes may run in other batches, and later results agree up to
+ * the rounding of differently shaped launches - the rule STCN_RESET_KEEP_FRAMES states above.
+ * stcn_engine_reset[_ex] empties the journal and keeps the depth; stcn_engine_clone gives the clone its source's depth and an EMPTY journal
+ * (the source's entries describe the source's tensors).  (No reference counterpart: InferenceCore has no undo.) */
+int stcn_engine_set_undo(stcn_engine *e, int depth);
+int stcn_engine_undo(stcn_engine *e, int32_t *idx_out, int32_t *still_interacted_out);
+/* depth as set, entries held now, device bytes their buffers hold; each pointer may be NULL.  A null engine returns STCN_E_INVALID. */
+int stcn_engine_get_undo(const stcn_engine *e, int32_t *depth, int32_t *entries, int64_t *bytes);
+
 /* Algorithmic work of the last interact() in FLOP (2 x MAC of every conv / GEMM issued). */
 int stcn_get_flops(const stcn_engine *e, double *flops);
 
@@ -435,6 +474,22 @@ int stcn_metrics_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pr
 int stcn_metrics_round(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev, const uint8_t *annotated_dev,
                        const uint8_t *noobj_dev, int T, int H, int W, int t0, int t1, int j_only, double no_object, uint8_t *gen_dev, uint8_t *scratch_dev,
                        int32_t *counts_dev, double *quality_dev, int32_t *select_dev);
+
+/* A TRIAL round scored beside the caller's rounds (enqueue only): the quality a round would have if `candidate` were annotated next, after
+ * the caller has tried that interaction on the engine (and before it takes it back with stcn_engine_undo) - what the upper-bound policy
+ * evaluates for every remaining frame (interactions/policies.py:98-113).  Binary masks; arguments as stcn_metrics_round, except:
+ *   annotated_dev  : the flags of the caller's last round, read only; the trial counts frame `candidate` (0 <= candidate < T) as annotated too
+ *   [t0, t1)       : the frames the trial can have changed - those strictly between the annotated neighbours of candidate; t0 == t1: none
+ *   counts_dev     : const int32 [T,6] - the counts of the caller's last round, the source for every frame outside [t0, t1)
+ *   span_gen_dev   : uint8 [(t1 - t0) * H * W] scratch - the evaluated masks of the span
+ *   scratch_dev    : uint8 [(t1 - t0) * H * W] scratch - its boundary map (unused when j_only);  span_counts_dev : int32 [(t1 - t0), 6] scratch
+ *   quality_dev    : double [T] OUT - per frame the value stcn_metrics_round would write after a real round with this annotation, to the bit:
+ *                    from the span's counts inside [t0, t1), from counts_dev outside, no_object for flagged frames
+ * Nothing else is written: no gen, no counts, no selection - the caller's round state is what it was.  Null pointers, t0 > t1, a span or a
+ * candidate outside [0, T) return STCN_E_INVALID before any device call. */
+int stcn_metrics_trial(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev, const uint8_t *annotated_dev,
+                       const uint8_t *noobj_dev, int candidate, int T, int H, int W, int t0, int t1, int j_only, double no_object,
+                       const int32_t *counts_dev, uint8_t *span_gen_dev, uint8_t *scratch_dev, int32_t *span_counts_dev, double *quality_dev);
 
 /* ---- the same for LABEL MAPS of k objects (multi-object annotation sessions) -------------------------------------------------
  * A label map is uint8, 0 = background, o in 1..k = object o (the engine's mask tensor for num_objects = k; the palette-index ground truth);
