@@ -88,12 +88,14 @@ PROTOTYPES = {
     "stcn_bench_memory_read_k": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, C.POINTER(_F), C.POINTER(C.c_int32)]),
     "stcn_bench_memory_read_km": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, C.POINTER(_F), C.POINTER(C.c_int32)]),
     "stcn_memread_plan": (_I, [_I, _I, C.POINTER(C.c_int32)]),
+    "stcn_attention_plan": (_I, [_I, C.POINTER(C.c_int32)]),
     "stcn_memread_scratch": (_I, [_I, C.POINTER(C.c_int64)]),
     "stcn_test_kernel": (_I, [C.c_char_p, _P, C.POINTER(_P), _I, C.POINTER(C.c_int64), _I, C.POINTER(_D), _I]),
     "stcn_test_fail_at": (_I, [_I]),
     "stcn_test_side_delay_us": (_I, [_I]),
     "stcn_test_decode": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "stcn_test_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "stcn_test_attention_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "stcn_test_fusion": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _I, _I, _P]),
     "stcn_metrics_jf_counts": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "stcn_metrics_j_counts": (_I, [_P, _P, _P, _I, _I, _I, _P]),

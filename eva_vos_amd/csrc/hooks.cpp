@@ -368,6 +368,14 @@ int stcn_memread_plan(int N, int Q, int32_t *plan7) {
     return STCN_OK;
 }
 
+int stcn_attention_plan(int hw, int32_t *plan5) {
+    if (!plan5 || hw < 1) { set_error("stcn_attention_plan: bad arguments"); return STCN_E_INVALID; }
+    const AttnPlan pl = attention_plan(hw);
+    const int32_t v[5] = {pl.steps, pl.qblocks, pl.NC, pl.spc, pl.NCeff};
+    for (int i = 0; i < 5; ++i) plan5[i] = v[i];
+    return STCN_OK;
+}
+
 int stcn_memread_scratch(int Q, int64_t *sizes5) {
     if (!sizes5 || Q < 1) { set_error("stcn_memread_scratch: bad arguments"); return STCN_E_INVALID; }
     const MemReadScratchSizes sz = memread_scratch_floats(Q);
@@ -396,15 +404,31 @@ int stcn_test_decode(const stcn_model *m, void *stream, const float *readout, co
 
 int stcn_test_attention(void *stream, const float *mk, const float *qk, const float *pos, const float *neg, int kk, int nh,
                         int nw, float *attn) {
-    if (!mk || !qk || !pos || !neg || !attn || kk < 1 || kk > STCN_MAX_OBJECTS + 1) { set_error("stcn_test_attention: bad arguments"); return STCN_E_INVALID; }
+    if (!pos || !neg) { set_error("stcn_test_attention: bad arguments"); return STCN_E_INVALID; }
+    return stcn_test_attention_ex(stream, mk, qk, pos, neg, kk, nh, nw, nullptr, nullptr, nullptr, nullptr, attn);
+}
+
+int stcn_test_attention_ex(void *stream, const float *mk, const float *qk, const float *pos, const float *neg, int kk, int nh, int nw,
+                           const float *msq_in, const float *pooled_in, float *pooled_out, float *amap_out, float *attn) {
+    const char *who = "stcn_test_attention_ex";
+    if (!mk || !qk || !attn || kk < 1 || kk > STCN_MAX_OBJECTS + 1) { set_error("%s: bad arguments (mk, qk, attn non-null, 1 <= kk <= %d; kk=%d)", who, STCN_MAX_OBJECTS + 1, kk); return STCN_E_INVALID; }
+    if (nh < 16 || nw < 16 || nh % 16 || nw % 16 || (long)nh * nw > MAX_FRAME_PIXELS) { set_error("%s: bad frame %d x %d (multiples of 16, at most 2^24 pixels)", who, nh, nw); return STCN_E_INVALID; }
+    // the masks of the interaction, or their pooled means from an earlier call - one of the two
+    if (pooled_in ? (pos || neg) : (!pos || !neg)) { set_error("%s: pos and neg, or pooled_in alone", who); return STCN_E_INVALID; }
     hipStream_t s = (hipStream_t)stream;
-    const int h = nh / 16, w = nw / 16;
+    const int h = nh / 16, w = nw / 16, nchp = attention_nchp(2 * kk);
     DevBuf msq, pooled, amap, gm, part;
     RC(gm.alloc((size_t)256 * h * w)); RC(part.alloc(attention_part_floats(kk, h * w)));
-    RC(msq.alloc(h * w + MEMREAD_MSQ_PAD)); RC(pooled.alloc((size_t)std::max(20, attention_nchp(2 * kk)) * h * w)); RC(amap.alloc((size_t)kk * 2 * h * w));
-    HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(h * w + MEMREAD_MSQ_PAD) * 4, s));
-    rowsumsq_launch(mk, h * w, 64, msq.p, s);
-    attention_read_launch(mk, msq.p, qk, pos, neg, kk, h, w, pooled.p, amap.p, attn, AttnScratch{gm.p, part.p}, s);
+    RC(pooled.alloc((size_t)std::max(20, nchp) * h * w)); RC(amap.alloc((size_t)kk * 2 * h * w));
+    if (!msq_in) {
+        RC(msq.alloc(h * w + MEMREAD_MSQ_PAD));
+        HIPCHK(hipMemsetAsync(msq.p, 0, (size_t)(h * w + MEMREAD_MSQ_PAD) * 4, s));
+        rowsumsq_launch(mk, h * w, 64, msq.p, s);
+    }
+    if (pooled_in) HIPCHK(hipMemcpyAsync(pooled.p, pooled_in, (size_t)nchp * h * w * 4, hipMemcpyDeviceToDevice, s));
+    attention_read_launch(mk, msq_in ? msq_in : msq.p, qk, pos, neg, kk, h, w, pooled.p, amap.p, attn, AttnScratch{gm.p, part.p}, s);
+    if (pooled_out) HIPCHK(hipMemcpyAsync(pooled_out, pooled.p, (size_t)nchp * h * w * 4, hipMemcpyDeviceToDevice, s));
+    if (amap_out) HIPCHK(hipMemcpyAsync(amap_out, amap.p, (size_t)kk * 2 * h * w * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     return STCN_OK;

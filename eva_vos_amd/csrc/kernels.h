@@ -272,6 +272,11 @@ void memory_read_launch(const MemRead &r, const MemReadScratch &scr, hipStream_t
 struct AttnScratch { float *gmax, *part; };   // [256][hw], attention_part_floats(kk, hw) ([16][hw][19] up to 8 objects)
 int attention_nchp(int nch);                          // channels 2 kk padded to the widths the pass kernel is instantiated for
 size_t attention_part_floats(int kk, int hw);
+// launch plan of the attention read of hw = h * w memory rows and as many queries: `steps` 64-row steps of the memory, `qblocks` workgroups of 64
+// queries, each walking NCeff chunks of spc steps (the last chunk may be shorter, none is empty); NC: the chunk count asked for before rounding
+// spc up (about 512 workgroups, at most 16 chunks - gmax holds 16 group maxima per chunk - and at most one per step)
+struct AttnPlan { int steps, qblocks, NC, spc, NCeff; };
+AttnPlan attention_plan(int hw);
 // pos == nullptr: `pooled` already holds attention_pool_launch's output for this interaction
 void attention_pool_launch(const float *pos, const float *neg, int kk, int h, int w, float *pooled, hipStream_t s);
 void attention_read_launch(const float *mk, const float *msq, const float *qk, const float *pos,

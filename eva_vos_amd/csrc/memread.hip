@@ -983,20 +983,28 @@ void attention_pool_launch(const float *pos, const float *neg, int kk, int h, in
     hipLaunchKernelGGL(area_pool16_kernel, dim3((unsigned)(((long)nchp * h * w + 255) / 256)), dim3(256), 0, s, pos, neg, kk, h, w, nchp, pooled);
 }
 
+static constexpr int ATTN_WAVES = 4;    // waves (of 16 queries) per workgroup of the two pass kernels
+AttnPlan attention_plan(int hw) {
+    AttnPlan p;
+    p.steps = (hw + HROWS - 1) / HROWS;
+    p.qblocks = (hw + 16 * ATTN_WAVES - 1) / (16 * ATTN_WAVES);
+    p.NC = (512 + p.qblocks - 1) / p.qblocks;
+    if (p.NC > MAXCHUNK) p.NC = MAXCHUNK;
+    if (p.NC > p.steps) p.NC = p.steps;
+    p.spc = (p.steps + p.NC - 1) / p.NC;
+    p.NCeff = (p.steps + p.spc - 1) / p.spc;
+    return p;
+}
+
 void attention_read_launch(const float *mk, const float *msq, const float *qk, const float *pos, const float *neg,
                            int kk, int h, int w, float *pooled, float *amap, float *attn, AttnScratch scr,
                            hipStream_t s) {
     const int hw = h * w, nch = kk * 2;
     if (pos) attention_pool_launch(pos, neg, kk, h, w, pooled, s);
-    constexpr int WAVES = 4;
-    const int steps = (hw + HROWS - 1) / HROWS;
-    const int qblocks = (hw + 16 * WAVES - 1) / (16 * WAVES);
-    int NC = (512 + qblocks - 1) / qblocks;
-    if (NC > MAXCHUNK) NC = MAXCHUNK;
-    if (NC > steps) NC = steps;
-    const int spc = (steps + NC - 1) / NC;
-    const int NCeff = (steps + spc - 1) / spc;
-    const dim3 grid(qblocks, NCeff);
+    constexpr int WAVES = ATTN_WAVES;
+    const AttnPlan pl = attention_plan(hw);
+    const int spc = pl.spc, NCeff = pl.NCeff;
+    const dim3 grid(pl.qblocks, NCeff);
     hipLaunchKernelGGL((colmax_pass_kernel<WAVES>), grid, dim3(64 * WAVES), 0, s, mk, msq, qk, hw, hw, spc, scr.gmax);
     const int nchp = attention_nchp(nch), pstr = attention_part_stride(nch);
     switch (nchp) {

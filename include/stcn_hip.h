@@ -380,6 +380,16 @@ int stcn_test_decode(const stcn_model *m, void *stream, const float *readout, co
  * -> attn [kk,2,nh*nw]. */
 int stcn_test_attention(void *stream, const float *mk, const float *qk, const float *pos,
                         const float *neg, int kk, int nh, int nw, float *attn);
+/* The same read with its stages in view; stcn_test_attention(...) = stcn_test_attention_ex(..., NULL, NULL, NULL, NULL, attn).  All optional:
+ *   msq        [hw16 + 64] |mk|^2 per memory row and 64 more floats that are read and never used; NULL: computed here
+ *   pooled_in  [hw16][nchp] the pooled masks an earlier call returned in pooled_out: the read then runs without pooling (pos = neg = NULL),
+ *              as the engine does on every frame of an interaction after the first.  Exactly one of (pos, neg) and pooled_in is given.
+ *   pooled_out [hw16][nchp] 16x16 block means, channel 2 r = pos[r], 2 r + 1 = neg[r], zero from 2 kk up to
+ *              nchp = 4, 8, 12 for 2 kk <= 4, 8, 12, else 2 kk rounded up to a multiple of 20
+ *   amap_out   [2 kk][hw16] pooled channels carried through the softmax, before the bilinear x16
+ * nh, nw: multiples of 16.  Arguments are checked before the first device call. */
+int stcn_test_attention_ex(void *stream, const float *mk, const float *qk, const float *pos, const float *neg, int kk, int nh, int nw,
+                           const float *msq, const float *pooled_in, float *pooled_out, float *amap_out, float *attn);
 
 /* FusionNet logit for one object (fusion_net.py:32-50).  img [1,3,nh,nw] NCHW; prev,curr [nh*nw];
  * attn [2,nh*nw] -> logit [nh*nw]. */
@@ -392,6 +402,11 @@ int stcn_test_fusion(const stcn_model *m, void *stream, const float *img, const 
  * plan7 = { 64-row steps, pass-1 sample stride, sampled steps, pass-1 chunks, steps per pass-1 chunk, pass-2 chunks,
  * steps per pass-2 chunk }.  Lets tests assert WHICH plan (sample stride 1/2/4/8) a comparison exercised. */
 int stcn_memread_plan(int N, int Q, int32_t *plan7);
+/* Launch plan of the fusion attention read of a frame of hw = h16 * w16 positions (what stcn_test_attention[_ex], stcn_stage_attention and
+ * the engine will run; it does not depend on the number of mask rows):
+ * plan5 = { 64-row steps of the memory, workgroups of 64 queries, chunks asked for, steps per chunk, chunks launched }.  The column maxima
+ * take 16 floats per chunk and query of a scratch of 256 per query: chunks launched <= 16.  Works without a GPU. */
+int stcn_attention_plan(int hw, int32_t *plan5);
 /* Scratch of that read for Q queries, in elements (what the engine and the hooks allocate; it depends on Q alone):
  * sizes5 = { cand_v, cand_i, cand_n, gmax, tau }.  Every (N, Q) plan fits: nc2 * Q * 50 <= cand_v = cand_i, nc2 * Q <= cand_n,
  * nc1 * Q * 64 <= gmax, 2 * Q * 50 <= gmax (the selection of a read of several objects reuses it), Q <= tau.  Works without a GPU. */

@@ -103,3 +103,34 @@ def up4_prob(logit):
 
 def aggregate_bound(figure):
     return max(1e-6, 4 * figure)
+
+
+# ---- shared by test_gpu_attention.py and test_gpu_stage_api.py
+def blob_masks(kk, H, W, g, noisy, zero_row=None):
+    """[kk,1,H,W] mask differences as an interaction leaves them: exact zeros except one to three elliptical blobs of uniform values per row;
+    rows r with r % 2 == noisy carry 0.02 * rand everywhere in addition; row `zero_row` stays all zero."""
+    out = torch.zeros(kk, 1, H, W)
+    u = lambda: torch.rand(1, generator=g).item()           # noqa: E731
+    for r in range(kk):
+        if r == zero_row:
+            continue
+        for _ in range(1 + int(3 * u())):
+            cy, cx, ry, rx = u() * H, u() * W, 4 + u() * H / 6, 4 + u() * W / 6
+            y0, y1, x0, x1 = max(0, int(cy - ry)), min(H, int(cy + ry) + 2), max(0, int(cx - rx)), min(W, int(cx + rx) + 2)
+            yy, xx = torch.meshgrid(torch.arange(y0, y1), torch.arange(x0, x1), indexing="ij")
+            m = (((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1).float() * torch.rand(y1 - y0, x1 - x0, generator=g)
+            out[r, 0, y0:y1, x0:x1] = torch.maximum(out[r, 0, y0:y1, x0:x1], m)
+        if r % 2 == noisy:
+            out[r, 0] += 0.02 * torch.rand(H, W, generator=g)
+    return out
+
+
+def attention_stages(mk, qk, pos, neg):
+    """The stages of oracle.stcn_oracle.attention_read in the precision of the operands: pooled [2 kk][hw] (channel 2 r = pos[r], 2 r + 1 =
+    neg[r]; F.interpolate(mode='area') to 1/16 = 16x16 block means), amap [2 kk][hw] = pooled @ Wm, and Wm [hw][hw] = the softmax over
+    the memory rows."""
+    from oracle import stcn_oracle as O
+    kk, hw = pos.shape[0], mk.shape[0]
+    pooled = torch.stack([F.avg_pool2d(pos, 16).reshape(kk, hw), F.avg_pool2d(neg, 16).reshape(kk, hw)], 1).reshape(2 * kk, hw)
+    Wm = torch.softmax(O.affinity_logits(mk, qk), dim=0)
+    return pooled, pooled @ Wm, Wm

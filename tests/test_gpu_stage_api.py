@@ -12,7 +12,7 @@ import torch.nn.functional as F
 from conftest import load_golden, rel_err, sample_of
 from eva_vos_amd import _lib, synth
 from eva_vos_amd.params import PropagationNetwork
-from gpu_util import torch_aggregate_wbg
+from gpu_util import aggregate_bound, blob_masks, torch_aggregate_wbg
 from oracle import stcn_oracle as O
 from test_oracle_golden import check_sequence_against_golden, run_sequence
 
@@ -137,6 +137,25 @@ def test_get_attention_matches_the_oracle(tag, nets, weights):
     d = float((out.cpu() - ref).abs().max())
     print(f"{tag} get_attention: max |d| vs oracle {d:.2e}")
     assert d < 1e-5
+
+
+@pytest.mark.parametrize("nh,nw", [(16, 16), (16, 48)])
+def test_get_attention_on_the_smallest_frames(nh, nw, nets):
+    """One and three 1/16-scale positions (a softmax over one row; one source row for the x16 upsample), b = 2 mask planes, random keys:
+    against the oracle in fp64, within gpu_util.aggregate_bound of the error of the oracle in fp32 (reference and bound of
+    test_gpu_attention.py)."""
+    h, w = nh // 16, nw // 16
+    g = torch.Generator().manual_seed(nh * nw)
+    mk, qk = torch.randn(1, 64, h, w, generator=g), torch.randn(1, 64, h, w, generator=g)
+    pos, neg = blob_masks(2, nh, nw, g, 1), blob_masks(2, nh, nw, g, 0)
+    rows = lambda x: x.flatten(2).transpose(1, 2)[0]      # noqa: E731
+    ref = O.attention_read(rows(mk).double(), rows(qk).double(), pos.double(), neg.double())
+    figure = float((O.attention_read(rows(mk), rows(qk), pos, neg).double() - ref).abs().max())
+    out = nets[0].get_attention(mk.unsqueeze(2).cuda(), pos.cuda(), neg.cuda(), qk.cuda())
+    assert tuple(out.shape) == (2, 2, nh, nw) and bool(torch.isfinite(out).all())
+    d = float((out.cpu().double() - ref).abs().max())
+    print(f"get_attention {nh} x {nw}: max |d| vs fp64 {d:.2e}, fp32 figure {figure:.2e}, bound {aggregate_bound(figure):.2e}")
+    assert d <= aggregate_bound(figure)
 
 
 @pytest.mark.parametrize("k", [1, 3, 32])
