@@ -70,6 +70,10 @@ PROTOTYPES = {
     "stcn_engine_get_undo": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "stcn_get_stats": (_I, [_P, C.POINTER(Stats)]),
     "stcn_get_key_frames": (_I, [_P, C.POINTER(C.c_int64)]),
+    "stcn_frame_gram_scratch": (_I, [_I, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "stcn_frame_sq_distances": (_I, [_P, _P, _I, C.c_int64, C.c_int64, _P, _P]),
+    "stcn_engine_frame_distances": (_I, [_P, _P]),
+    "stcn_engine_frame_features": (_I, [_P, _I, _P]),
     "stcn_get_flops": (_I, [_P, C.POINTER(_D)]),
     "stcn_last_conv_path": (C.c_char_p, []),
     "stcn_test_conv_trace": (_I, [_I]),

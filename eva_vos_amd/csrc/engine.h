@@ -211,6 +211,7 @@ struct stcn_engine {
     std::vector<char> vparts_ready;    // frame -> value-encoder frame parts (vd, vc) are in its slot
     int n_cached = 0;
     float *cache = nullptr; size_t slot_floats = 0;
+    double *gram_scratch = nullptr;    // stcn_engine_frame_distances: partial Gram tiles (frame_gram_scratch_bytes), taken from the pool at the first call
     // memory bank: rows = slots * hw16
     int bank_cap = 0, n_certain = 0;
     float *bank_k = nullptr, *bank_msq = nullptr, *bank_v = nullptr;

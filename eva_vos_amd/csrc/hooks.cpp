@@ -477,6 +477,35 @@ int stcn_metrics_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pr
     return STCN_OK;
 }
 
+// ---- frame distances (frame_select.hip): the generic entry; stcn_engine_frame_distances (engine.cpp) runs the same launch on the key cache
+static bool frame_gram_shape_ok(const char *who, int T, int64_t K) {
+    if (T < 1 || T > FRAME_GRAM_MAX_T) { set_error("%s: T=%d outside 1..%d", who, T, FRAME_GRAM_MAX_T); return false; }
+    if (K < 4 || K % 4 != 0) { set_error("%s: K=%lld is not a multiple of 4 that is >= 4", who, (long long)K); return false; }
+    return true;
+}
+
+int stcn_frame_gram_scratch(int T, int64_t K, int64_t *bytes, int32_t *slices) {
+    if (!frame_gram_shape_ok("stcn_frame_gram_scratch", T, K)) return STCN_E_INVALID;
+    if (bytes) *bytes = (int64_t)frame_gram_scratch_bytes(T, (long)K);
+    if (slices) *slices = frame_gram_plan(T, (long)K).slices;
+    return STCN_OK;
+}
+
+int stcn_frame_sq_distances(void *stream, const float *x_dev, int T, int64_t K, int64_t stride, void *scratch_dev, double *dist_dev) {
+    const char *who = "stcn_frame_sq_distances";
+    if (!x_dev || !scratch_dev || !dist_dev) { set_error("%s: null pointer (x_dev=%p scratch_dev=%p dist_dev=%p)", who, (const void *)x_dev, scratch_dev, (void *)dist_dev); return STCN_E_INVALID; }
+    if (!frame_gram_shape_ok(who, T, K)) return STCN_E_INVALID;
+    if (stride < K || stride % 4 != 0) { set_error("%s: stride=%lld is not a multiple of 4 that is >= K=%lld", who, (long long)stride, (long long)K); return STCN_E_INVALID; }
+    if ((uintptr_t)x_dev % 16 != 0 || (uintptr_t)scratch_dev % 8 != 0 || (uintptr_t)dist_dev % 8 != 0) {
+        set_error("%s: x_dev=%p must be 16-byte aligned (scratch_dev, dist_dev: 8)", who, (const void *)x_dev);
+        return STCN_E_INVALID;
+    }
+    FrameIndex index;
+    for (int t = 0; t < FRAME_GRAM_MAX_T; ++t) index.v[t] = t < T ? t : 0;
+    frame_gram_launch(x_dev, index, (long)stride, T, (long)K, static_cast<double *>(scratch_dev), dist_dev, (hipStream_t)stream);
+    return launch_status("frame distances");
+}
+
 int stcn_metrics_objects_scratch(int k, int T, int H, int W, int64_t *bytes) {
     if (!metric_args_ok("stcn_metrics_objects_scratch", true, k, T, H, W, 2, {bytes})) return STCN_E_INVALID;
     *bytes = (int64_t)label_scratch_bytes(k, T, H, W);

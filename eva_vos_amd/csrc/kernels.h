@@ -314,6 +314,22 @@ void trial_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, co
                         int T_all, int H, int W, int t0, int t1, int radius, double no_object, const int *base, uint8_t *span_gen, uint8_t *bmap,
                         int *span_counts, double *quality, hipStream_t s);
 
+// ---------------------------------------------------------------- frame distances (frame_select.hip)
+// dist [T][T] fp64 = squared L2 distances between T vectors of K fp32 values, vector t at x + index.v[t] * stride (16-byte aligned: x and
+// stride multiples of 4 floats, K % 4 == 0, K >= 4, 1 <= T <= FRAME_GRAM_MAX_T).  The Gram matrix is accumulated in fp64 on the matrix cores
+// (v_mfma_f64_16x16x4_f64), K cut into plan.slices slices of plan.len values - a multiple of the k-step, slices * len >= K, no slice empty -
+// whose partial 16 x 16 tiles [slices][pairs][16][16] go through `scratch` and are summed in slice order: symmetric, zero diagonal, the same
+// bits on every run.  index travels as a kernel argument.
+constexpr int FRAME_GRAM_MAX_T = 106;           // the frames of the key cache
+constexpr int FRAME_GRAM_KSTEP = 32;            // k values a wave consumes per step
+constexpr int FRAME_GRAM_MAX_SLICES = 512;      // two workgroups of four waves per compute unit
+struct FrameIndex { int v[FRAME_GRAM_MAX_T]; };
+struct FrameGramPlan { int slices; long len; int nt, pairs; };      // nt tiles of 16 frames, pairs = nt (nt + 1) / 2 tiles of the upper triangle
+FrameGramPlan frame_gram_plan(int T, long K);                       // pure host code
+size_t frame_gram_scratch_bytes(int T, long K);                     // from that plan and from nothing else: slices * pairs * 2048
+void frame_gram_launch(const float *x, const FrameIndex &index, long stride, int T, long K, double *scratch, double *dist, hipStream_t s,
+                       hipEvent_t *ev_gram = nullptr, hipEvent_t *ev_red = nullptr);
+
 // pure fp32-MFMA load (no memory traffic): launches `grid` workgroups of 12 waves x iters x 12 MFMAs, returns the FLOP of the launch
 double mfma_probe_launch(float *out, int grid, int iters, hipStream_t s);
 

@@ -1,8 +1,8 @@
 """Annotation-policy evaluation on the HIP engine, sharded over the GPUs of one node (BASELINE config 5, mask policies).
 
 Own counterpart of the reference driver ``eval_annotation_method.py:118-190`` for the policies whose annotations are
-ground-truth masks - ``oracle_mask``, ``rand_mask``, ``qnet_mask``, ``upper_bound_mask`` (``interactions/mask.py:10-39,
-42-71,74-103,196-227``) - with their helpers ``initialize`` / ``not_avail_frames`` / ``eval_processor_metric``
+ground-truth masks - ``oracle_mask``, ``rand_mask``, ``qnet_mask``, ``upper_bound_mask``, ``l2_mask`` (``interactions/mask.py:10-39,
+42-71,74-103,196-227,159-193``) - with their helpers ``initialize`` / ``not_avail_frames`` / ``eval_processor_metric``
 (``interactions/eval.py:27-117``) and the frame selectors of ``interactions/policies.py``.  The click / bbox policies
 and ``eva_vos`` itself additionally need SAM (``segment_anything``) and the PPO agent, which north_star leaves on stock
 PyTorch-ROCm and which are not installed offline; they call the same ``InferenceCore.interact`` boundary.
@@ -11,6 +11,9 @@ Differences by design:
 
 * J / J&F per frame come from the device (``stcn_metrics_jf_counts``) - masks never visit the host per round;
 * QNet frame selection keeps features on the device (``eva_vos_amd.qnet``);
+* ``l2_mask`` applies the reference's rule (farthest frame, in L2, from every annotated one) to the ``f16`` features the engine has cached
+  for the clip, NOT to the reference's ImageNet / DINO extractors: no second network, one distance matrix per video
+  (``InferenceCore.frame_distances``), clips of at most 106 frames;
 * two samples are in flight per GPU (host thread + HIP stream each, ``--lanes``): +9..17 % rounds/s;
 * the per-object sessions of a video share one engine and the frame features it has computed (``fq_driver.LaneCores``; same rows;
   ``--no-share-frames`` switches it off), so videos, not samples, are dealt to ranks and lanes;
@@ -36,15 +39,23 @@ import numpy as np
 import torch
 
 from . import metrics, shard
+from .frame_select import farthest_frame
 from .fq_driver import NO_OBJECT, ClipDataset, LaneCores, annotation_session, frame_quality, lane_engine_options, run_lanes
 
-POLICIES = ("oracle_mask", "rand_mask", "qnet_mask", "upper_bound_mask")
-MULTI_OBJECT_POLICIES = ("oracle_mask", "rand_mask")          # QNet takes one binary mask; the upper bound builds on the one-object scorer
+POLICIES = ("oracle_mask", "rand_mask", "qnet_mask", "upper_bound_mask", "l2_mask")
+# QNet takes one binary mask; the upper bound builds on the one-object scorer; the l2 selector needs no mask at all
+MULTI_OBJECT_POLICIES = ("oracle_mask", "rand_mask", "l2_mask")
 MAX_OBJECTS = 32                                              # STCN_MAX_OBJECTS
 MASK_SECONDS, SKIP_SECONDS = 80, 3            # annotation cost model of interactions/mask.py:33-36
 
 
 KEY_CACHE_FRAMES = 106                                       # the engine's key cache: a clip of at most this many frames never recycles a slot
+
+
+def _check_l2_clip(policy: str, T: int, what: str):
+    """``l2_mask`` reads every frame's features out of the key cache: a longer clip recycles its slots and is refused before any work."""
+    if policy == "l2_mask" and T > KEY_CACHE_FRAMES:
+        raise ValueError(f"l2_mask: {what} has {T} frames, the policy needs every frame's features in the key cache, which holds at most {KEY_CACHE_FRAMES}")
 
 
 def _upper_bound_frame(processor, gt, gt_thw, frames, metric, stats=None):
@@ -105,11 +116,14 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
     ``upper_bound_mask`` tries its candidates on the session's own engine and takes them back (``_upper_bound_frame_in_place``) when the clip
     fits the key cache, on deep copies of the engine (``_upper_bound_frame``) when it does not: decided by the clip length alone.
     ``stats`` (optional dict): ``propagated_frames`` and ``interactions`` of the session's own rounds are added to it, and for the upper
-    bound ``trial_interactions`` (candidates tried) and ``engine_clones`` (deep copies made)."""
+    bound ``trial_interactions`` (candidates tried) and ``engine_clones`` (deep copies made).
+    ``l2_mask`` chooses ``farthest_frame(processor.frame_distances(), frames)``; a clip longer than the key cache raises ValueError before the
+    processor is touched; ``stats["frame_distance_passes"]`` counts the engine passes the session added (0 when the core came with the matrix)."""
     assert policy in POLICIES, policy
     if multi_object and policy not in MULTI_OBJECT_POLICIES:
         raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
     T = sample["num_frames"]
+    _check_l2_clip(policy, T, f"clip {sample.get('name', '?')}")
     dev = processor.prob.device
     rng = rng or random
     # the evaluation of a round stays on the device (metrics.RoundScorer): one int per round crosses PCIe for the oracle policy, the
@@ -139,6 +153,8 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
         if policy == "qnet_mask":
             from .qnet import qnet_frame_selection
             return qnet_frame_selection(qnet, images, gen.float(), frames)
+        if policy == "l2_mask":
+            return farthest_frame(processor.frame_distances(), frames)
         if in_place:
             return _upper_bound_frame_in_place(processor, scorer, gt, frames, stats)
         return _upper_bound_frame(processor, gt, gt_thw, frames, metric, stats)
@@ -151,11 +167,14 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
     depth = processor.undo_state()["depth"] if in_place else 0
     if in_place:
         processor.set_undo_depth(max(depth, 1))
+    passes = processor.frame_distance_passes if policy == "l2_mask" else 0
     try:
         frames, gens = annotation_session(processor, scorer, T, rounds, annotate, choose, keep_gen=policy == "qnet_mask", stats=stats)
     finally:
         if in_place:
             processor.set_undo_depth(depth)                        # the core goes back to its lane as it came
+    if policy == "l2_mask":
+        stats["frame_distance_passes"] = stats.get("frame_distance_passes", 0) + processor.frame_distance_passes - passes
     empty, scored = scorer.empty_host, len(gens)
     times = [MASK_SECONDS] + [SKIP_SECONDS if empty[f] else MASK_SECONDS for f in frames[1:]]
     q = scorer.qualities()
@@ -174,7 +193,8 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
     (rows: sample id, round, mu_metric, annotation_time, annotated frame, T, then T per-frame values, NaN-padded).
     `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited), `interactions`, `key_frames_encoded` (frames that
-    went through the key encoder) and `engines_created` are added to it, for `upper_bound_mask` also `trial_interactions` and `engine_clones`.
+    went through the key encoder) and `engines_created` are added to it, for `upper_bound_mask` also `trial_interactions` and `engine_clones`,
+    for `l2_mask` also `frame_distance_passes` (one per video when its sessions share an engine).
     `share_frames` (per-object mode; the protocol and the rows stay the reference's): the sessions of a video's objects run one after the
     other on ONE engine that keeps the clip and its frame features between them (fq_driver.LaneCores) - videos, not samples, are dealt to
     ranks and lanes.  False: a fresh engine and a fresh upload per sample, samples dealt one by one.
@@ -194,6 +214,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         if k > MAX_OBJECTS:
             raise ValueError(f"video {v} has {k} objects: a multi-object session holds at most {MAX_OBJECTS}")
     t_max = max(s[2] for s in ds.samples)
+    _check_l2_clip(policy, t_max, "the longest clip")
     share_frames = share_frames and not multi_object
     if share_frames:
         mine = sorted(shard.lpt_assign_grouped([s[2] for s in ds.samples], [s[0] for s in ds.samples], world)[rank])      # the objects of a video share an engine
@@ -218,7 +239,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
                 stats["session_s"] = stats.get("session_s", 0.0) + time.perf_counter() - t_s
                 stats["propagated_frames"] = stats.get("propagated_frames", 0) + res["propagated_frames"]
                 stats["interactions"] = stats.get("interactions", 0) + len(res["mu_metrics"])
-                for n in ("trial_interactions", "engine_clones"):
+                for n in ("trial_interactions", "engine_clones", "frame_distance_passes"):
                     if n in session:
                         stats[n] = stats.get(n, 0) + session[n]
         if multi_object:

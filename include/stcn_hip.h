@@ -208,6 +208,38 @@ int stcn_engine_undo(stcn_engine *e, int32_t *idx_out, int32_t *still_interacted
 /* depth as set, entries held now, device bytes their buffers hold; each pointer may be NULL.  A null engine returns STCN_E_INVALID. */
 int stcn_engine_get_undo(const stcn_engine *e, int32_t *depth, int32_t *entries, int64_t *bytes);
 
+/* ---- cached frame features and the distances between them -----------------------------------------------------------------
+ * For frame selectors that need neither ground truth nor a trained network: the reference's l2_mask policy (interactions/mask.py:159-193)
+ * annotates next the frame whose features lie farthest, in L2, from every annotated frame (get_frame_l2 / get_min_l2_dist,
+ * interactions/policies.py:21-36,69-88) and runs a second pretrained encoder over the clip for them.  Here the features exist already: after
+ * the first interaction of a clip of at most STCN_FRAME_GRAM_MAX_T frames every frame's ResNet-50 f16 map [hw16][1024] sits in its
+ * key-cache slot, a function of the frame and the model only.
+ *
+ * Squared L2 distances between T vectors of K fp32 values: dist[i][j] = |x_i - x_j|^2 as fp64 [T,T], symmetric to the bit, zero diagonal,
+ * the same bits on every run.  |a|^2 + |b|^2 - 2 a.b cancels between near-equal frames, so the Gram matrix is accumulated in fp64
+ * (v_mfma_f64_16x16x4_f64: the product of two fp32 values is exact in fp64, what remains is fp64 summation error,
+ * <= K * 2^-53 * (|x_i|^2 + |x_j|^2)).  K is cut into slices whose partial sums pass through a scratch buffer:
+ * stcn_frame_gram_scratch gives its size in bytes and the slice count (each pointer may be NULL) from the host-side plan alone - no GPU is
+ * needed.  1 <= T <= STCN_FRAME_GRAM_MAX_T, K >= 4 and K % 4 == 0, else STCN_E_INVALID. */
+#define STCN_FRAME_GRAM_MAX_T 106
+int stcn_frame_gram_scratch(int T, int64_t K, int64_t *bytes, int32_t *slices);
+/* The generic entry (enqueue only): vector t starts at x_dev + t * stride.  A null pointer, T outside 1..106, K < 4 or K % 4 != 0,
+ * stride < K or stride % 4 != 0, and an x_dev that is not 16-byte aligned return STCN_E_INVALID with a message that names the value,
+ * before any device call.  Floats between K and stride are never read. */
+int stcn_frame_sq_distances(void *stream, const float *x_dev, int T, int64_t K, int64_t stride, void *scratch_dev, double *dist_dev /*[T,T]*/);
+/* The same for the engine's clip, on the engine's stream (enqueue only): vector t is the cached f16 map of frame t, read in place from its
+ * key-cache slot; the scratch comes from the engine-buffer pool at the first call.  STCN_E_STATE, with a message that says which: the engine
+ * is in a failed state; the clip is longer than the key cache (T > 106); some frame holds no slot - before the first interaction and
+ * after a plain reset (STCN_RESET_KEEP_FRAMES keeps them: the next object's session may call at once).
+ * Ordering: every slot write is on the engine's stream or joined into it before stcn_interact returns - a sweep's stream waits for the key
+ * encoder's event of every frame it visits (no such wait is left pending when an interaction ends: keys are only enqueued for frames of the
+ * sweep in progress), the stream of a concurrent backward sweep is joined before the argmax, and a failed interaction is refused here. */
+int stcn_engine_frame_distances(stcn_engine *e, double *dist_dev /*[T,T]*/);
+/* One cached map: an asynchronous device-to-device copy of frame `frame`'s f16 [hw16,1024] (rows = 1/16-scale positions, the engine's
+ * layout) on the engine's stream.  Same state rules (only `frame` has to hold a slot); a frame outside [0,T) returns STCN_E_INVALID.
+ * (No reference counterpart: the reference's callers would call prop_net.encode_key themselves.) */
+int stcn_engine_frame_features(stcn_engine *e, int frame, float *f16_dev /*[hw16,1024]*/);
+
 /* Algorithmic work of the last interact() in FLOP (2 x MAC of every conv / GEMM issued). */
 int stcn_get_flops(const stcn_engine *e, double *flops);
 
