@@ -157,7 +157,8 @@ bool wino4_plan(const ConvP &p, int min_wg, size_t v_cap, size_t slab_floats, Co
 void wino4_launch(const ConvP &p, const ConvPlan &pl, float *V, hipStream_t s, hipEvent_t *const *ev_in = nullptr,
                   hipEvent_t *const *ev_gemm = nullptr, hipEvent_t *ev_red = nullptr);
 void wino4_transform_weights(const float *w, int N, int Cin, int Kp, float *U);
-// The family switches, read once per process: STCN_WINOGRAD (0: no F(2x2) weights, workspace or launches) and STCN_WINO4
+// The family switches, read once per process: STCN_WINOGRAD (0: no F(2x2) weights or launches; the V workspace
+// is shared and exists while either family is on) and STCN_WINO4
 // (0 off, 1 on for flagged layers with enough workgroups (default), 2 whenever the shape allows)
 bool wino_enabled();
 int wino4_mode();

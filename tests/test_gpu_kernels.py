@@ -112,8 +112,9 @@ def test_the_path_table_covers_every_case():
     assert len(PATHS) == len(CONVS)
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout,K,s,flags,splitk,path", [c + (p,) for c, p in zip(CONVS, PATHS)])
-def test_conv_matches_fp64_reference(B, H, W, Cin, Cout, K, s, flags, splitk, path, monkeypatch):
+def conv_fp64_case(B, H, W, Cin, Cout, K, s, flags):
+    """The seeded operands of one CONVS-style case - bias always, a residual for batch 2 and the FusionNet shape - and F.conv2d of them in
+    fp64 (ReLUs as flags bits 0 / 1 say): x, w, b, res (or None), ref, OH, OW.  Shared with tests/switch_arm_cases.py."""
     g = torch.Generator().manual_seed(Cin * 131 + Cout * 7 + K)
     x = torch.randn(B, Cin, H, W, generator=g)
     w = torch.randn(Cout, Cin, K, K, generator=g) * (2.0 / (Cin * K * K)) ** 0.5
@@ -127,6 +128,12 @@ def test_conv_matches_fp64_reference(B, H, W, Cin, Cout, K, s, flags, splitk, pa
         ref = ref + res.double()
     if flags & 2:
         ref = F.relu(ref)
+    return x, w, b, res, ref, OH, OW
+
+
+@pytest.mark.parametrize("B,H,W,Cin,Cout,K,s,flags,splitk,path", [c + (p,) for c, p in zip(CONVS, PATHS)])
+def test_conv_matches_fp64_reference(B, H, W, Cin, Cout, K, s, flags, splitk, path, monkeypatch):
+    x, w, b, res, ref, OH, OW = conv_fp64_case(B, H, W, Cin, Cout, K, s, flags)
     # Winograd-eligible shapes run under BOTH GEMM instances (16 waves x 1 position, 8 waves x 2 positions), whatever the
     # default choice for their channel count is
     monkeypatch.setenv("STCN_WINO_MIN_CIN", "64")          # the opt-in F(2x2) path of 64-channel layers stays tested

@@ -55,19 +55,19 @@ def test_a_listed_bank_runs_a_multi_chunk_sampled_plan():
     assert pl["nc2"] >= 2 and pl["ss"] >= 2 and pl["nc1"] >= 2, pl
 
 
-@pytest.mark.parametrize("bank", BANKS, ids=lambda b: f"N{b[0]}-Q{b[1]}-k{b[2]}")
-@pytest.mark.parametrize("top_k", [1, 2, 20, 49])
-def test_memory_read_k_matches_oracle(top_k, bank, monkeypatch):
-    """Inputs drawn as test_gpu_kernels.test_memory_read_matches_oracle draws them.  Clear-cut queries (gap between the top_k-th and the
-    next score >= 1e-4): the oracle's selection, weights and read-out.  Near-tie queries (at most 4 % of a case, asserted): any valid
-    top-k of the fp64 scores with its own weights and read-out."""
-    N, Q, k, scale = bank
-    N = top_k if N == "K" else (max(36, top_k) if N == "36" else N)
-    monkeypatch.setattr(O, "TOP_K", top_k)
+def random_bank(N, Q, k, scale=1.0):
+    """mk [N,64], mv [k,N,512], qk [Q,64] drawn as test_gpu_kernels.test_memory_read_matches_oracle draws them"""
     g = torch.Generator().manual_seed(N + Q)
     mk = torch.randn(N, 64, generator=g) * scale
     qk = torch.randn(Q, 64, generator=g) * scale
     mv = torch.randn(k, N, 512, generator=g)
+    return mk, mv, qk
+
+
+def check_read_k_against_oracle(mk, mv, qk, top_k):
+    """The statements of test_memory_read_k_matches_oracle for one bank (O.TOP_K is already top_k): returns the numbers of near-tie queries
+    and of queries that selected other rows than the oracle.  Shared with tests/switch_arm_cases.py."""
+    N, Q, k = mk.shape[0], qk.shape[0], mv.shape[0]
     oi, ow, oro, gap = O.memory_read(mk, mv, qk, return_gap=True)
     assert oi.shape == (Q, top_k)
     gi, gw, gro = _memread_k(mk, mv, qk, top_k)
@@ -85,13 +85,24 @@ def test_memory_read_k_matches_oracle(top_k, bank, monkeypatch):
     err = (gro - oro).abs().amax((0, 2)) / oro.abs().max()
     assert err[same].max() < 2e-5, float(err[same].max())
     _check_own(mk, mv, qk, gi, gw, gro, torch.nonzero(~same).flatten().tolist())
+    return int(near.sum()), int((~same).sum())
 
 
-@pytest.mark.parametrize("top_k", [1, 20])
-def test_rising_scores_cut_full_lists_back_to_top_k(top_k, monkeypatch):
+@pytest.mark.parametrize("bank", BANKS, ids=lambda b: f"N{b[0]}-Q{b[1]}-k{b[2]}")
+@pytest.mark.parametrize("top_k", [1, 2, 20, 49])
+def test_memory_read_k_matches_oracle(top_k, bank, monkeypatch):
+    """Inputs drawn as test_gpu_kernels.test_memory_read_matches_oracle draws them.  Clear-cut queries (gap between the top_k-th and the
+    next score >= 1e-4): the oracle's selection, weights and read-out.  Near-tie queries (at most 4 % of a case, asserted): any valid
+    top-k of the fp64 scores with its own weights and read-out."""
+    N, Q, k, scale = bank
+    N = top_k if N == "K" else (max(36, top_k) if N == "36" else N)
+    monkeypatch.setattr(O, "TOP_K", top_k)
+    check_read_k_against_oracle(*random_bank(N, Q, k, scale), top_k)
+
+
+def rising_scores_bank():
     """The bank of test_memory_read_rising_scores_forces_many_selects: every tile beats the running threshold, the pass-2 lists
     overflow and are cut back to their best top_k again and again."""
-    monkeypatch.setattr(O, "TOP_K", top_k)
     N, Q = 4000, 48
     u = torch.randn(64, generator=torch.Generator().manual_seed(3))
     u = u / u.norm() * 3.0
@@ -99,10 +110,27 @@ def test_rising_scores_cut_full_lists_back_to_top_k(top_k, monkeypatch):
     mk = a * u[None, :] + 1e-3 * torch.randn(N, 64, generator=torch.Generator().manual_seed(4))
     qk = u[None, :].repeat(Q, 1) + 0.05 * torch.randn(Q, 64, generator=torch.Generator().manual_seed(5))
     mv = torch.randn(1, N, 512, generator=torch.Generator().manual_seed(6))
+    return mk, mv, qk
+
+
+def check_rising_scores_read(top_k):
+    """(O.TOP_K is already top_k) weights and read-out of the rising-scores bank within 5e-5 of the oracle's; returns the two figures"""
+    mk, mv, qk = rising_scores_bank()
+    N = mk.shape[0]
     oi, ow, oro = O.memory_read(mk, mv, qk)
     gi, gw, gro = _memread_k(mk, mv, qk, top_k)
-    assert (_dense(gi, gw, N) - _dense(oi, ow, N)).abs().max() < 5e-5
-    assert (gro - oro).abs().max() / oro.abs().max() < 5e-5
+    dw, err = float((_dense(gi, gw, N) - _dense(oi, ow, N)).abs().max()), float((gro - oro).abs().max() / oro.abs().max())
+    assert dw < 5e-5
+    assert err < 5e-5
+    return dw, err
+
+
+@pytest.mark.parametrize("top_k", [1, 20])
+def test_rising_scores_cut_full_lists_back_to_top_k(top_k, monkeypatch):
+    """The bank of test_memory_read_rising_scores_forces_many_selects: every tile beats the running threshold, the pass-2 lists
+    overflow and are cut back to their best top_k again and again."""
+    monkeypatch.setattr(O, "TOP_K", top_k)
+    check_rising_scores_read(top_k)
 
 
 def test_exact_ties_at_top_k_20(monkeypatch):
