@@ -373,8 +373,10 @@ def test_memory_read_at_config3_bank_sizes_matches_oracle(T, Q, k):
 
 
 def test_memory_read_rising_scores_forces_many_selects():
-    """Scores increase with the row index, so every tile beats the running threshold (worst case for
-    the streaming top-k: a select every tile)."""
+    """Scores increase with the row index.  Written for the one-pass streaming read, where every tile beat the running threshold and
+    forced a select.  Under the two-pass read pass 1's threshold lands about 50 rows from the end of the bank: all candidates sit in
+    one short chunk, its list is 32 entries long (CAP2 = 64), and neither the cut-back inside pass 2 nor the write-out select runs.
+    Lists that overflow: test_gpu_memread_lists.py; the lengths on this bank: test_memread_lists.py."""
     N, Q = 4000, 48
     u = torch.randn(64, generator=torch.Generator().manual_seed(3))
     u = u / u.norm() * 3.0

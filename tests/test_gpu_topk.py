@@ -101,8 +101,10 @@ def test_memory_read_k_matches_oracle(top_k, bank, monkeypatch):
 
 
 def rising_scores_bank():
-    """The bank of test_memory_read_rising_scores_forces_many_selects: every tile beats the running threshold, the pass-2 lists
-    overflow and are cut back to their best top_k again and again."""
+    """The bank of test_memory_read_rising_scores_forces_many_selects: scores rise with the row index.  Under the two-pass read the
+    threshold of pass 1 lands about 50 rows from the end of the bank and all candidates sit in one short chunk: its longest list is 32,
+    25 or 8 entries at top_k = 50, 20 or 1 (tests/test_memread_lists.py prints them), below the 64 a list holds, so no list overflows
+    and none is cut back inside pass 2."""
     N, Q = 4000, 48
     u = torch.randn(64, generator=torch.Generator().manual_seed(3))
     u = u / u.norm() * 3.0
@@ -127,8 +129,9 @@ def check_rising_scores_read(top_k):
 
 @pytest.mark.parametrize("top_k", [1, 20])
 def test_rising_scores_cut_full_lists_back_to_top_k(top_k, monkeypatch):
-    """The bank of test_memory_read_rising_scores_forces_many_selects: every tile beats the running threshold, the pass-2 lists
-    overflow and are cut back to their best top_k again and again."""
+    """The rising-scores bank at top_k < 50: the longest pass-2 list is 25 (top_k = 20) or 8 (top_k = 1) entries, so only the select at
+    the chunk's write-out (a list longer than top_k) runs here; the name dates from the one-pass read.  Lists that overflow their 64
+    entries and are cut back inside pass 2: tests/test_gpu_memread_lists.py."""
     monkeypatch.setattr(O, "TOP_K", top_k)
     check_rising_scores_read(top_k)
 
