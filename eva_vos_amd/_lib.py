@@ -109,6 +109,11 @@ PROTOTYPES = {
     "stcn_metrics_objects_jf_counts": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "stcn_metrics_objects_j_counts": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "stcn_metrics_objects_round": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P]),
+    "stcn_metrics_round_typed": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P]),
+    "stcn_robot_scratch": (_I, [_I, _I, C.POINTER(C.c_int64)]),
+    "stcn_robot_click": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P]),
+    "stcn_robot_bbox": (_I, [_P, _P, _I, _I, _P]),
+    "stcn_robot_best_mask": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "stcn_bench_conv": (_I, [_P] + [_I] * 11 + [C.POINTER(_F), C.POINTER(_D)]),
     "stcn_bench_mfma_rate": (_I, [_P, _I, C.POINTER(_F), C.POINTER(_F)]),
     "stcn_pool_release": (_I, []),

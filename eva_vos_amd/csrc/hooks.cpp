@@ -531,10 +531,11 @@ int stcn_metrics_objects_j_counts(void *stream, const uint8_t *gt_dev, const uin
 // [t0, t1) are composed and counted now; the counts (and gen) of the other frames are the caller's from earlier rounds.
 static int metrics_round(const char *who, bool labels, void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev,
                          const uint8_t *annotated_dev, const uint8_t *flags_dev, int k, int T, int H, int W, int t0, int t1, int j_only, double no_object,
-                         uint8_t *gen_dev, void *scratch_dev, int32_t *counts_dev, double *object_quality_dev, double *quality_dev, int32_t *select_dev) {
+                         uint8_t *gen_dev, void *scratch_dev, int32_t *counts_dev, double *object_quality_dev, double *quality_dev, int32_t *select_dev,
+                         bool typed = false, const uint8_t *annot_dev = nullptr) {
     const void *unused = who;       // in the place of a pointer that this form of the call does not read
     if (!metric_args_ok(who, labels, k, T, H, W, 2, {masks_dev, gt_dev, annotated_dev, flags_dev, gen_dev, counts_dev, labels ? object_quality_dev : unused,
-                                                    quality_dev, select_dev, j_only ? unused : scratch_dev}))
+                                                    quality_dev, select_dev, j_only ? unused : scratch_dev, typed ? annot_dev : unused}))
         return STCN_E_INVALID;
     if (lh < 0 || lw < 0 || lh + H > nh || lw + W > nw) { set_error("%s: the %d x %d crop at (%d, %d) leaves the %d x %d tensor", who, H, W, lh, lw, nh, nw); return STCN_E_INVALID; }
     if (t0 < 0 || t1 > T || t0 >= t1) { set_error("%s: frames [%d, %d) are not a non-empty range inside [0, %d)", who, t0, t1, T); return STCN_E_INVALID; }
@@ -542,9 +543,16 @@ static int metrics_round(const char *who, bool labels, void *stream, const uint8
     void *scratch = j_only ? nullptr : (char *)scratch_dev + (labels ? label_scratch_bytes(k, t0, H, W) : t0 * hw);      // the scratch of frame t0
     round_score_launch(masks_dev + (size_t)t0 * nh * nw, nh, nw, lh, lw, gt_dev + t0 * hw, annotated_dev + t0, flags_dev, labels ? k : 0, t1 - t0, H, W,
                        j_only ? -1 : bound_radius(H, W), no_object, gen_dev + t0 * hw, scratch, counts_dev + (size_t)t0 * 6, T, object_quality_dev,
-                       quality_dev, select_dev, (hipStream_t)stream, t0);
+                       quality_dev, select_dev, (hipStream_t)stream, t0, typed ? annot_dev + t0 * hw : nullptr);
     HIPCHK(hipGetLastError());
     return STCN_OK;
+}
+
+int stcn_metrics_round_typed(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev, const uint8_t *type_dev,
+                             const uint8_t *annot_dev, const uint8_t *noobj_dev, int T, int H, int W, int t0, int t1, int j_only, double no_object,
+                             uint8_t *gen_dev, uint8_t *scratch_dev, int32_t *counts_dev, double *quality_dev, int32_t *select_dev) {
+    return metrics_round("stcn_metrics_round_typed", false, stream, masks_dev, nh, nw, lh, lw, gt_dev, type_dev, noobj_dev, 0, T, H, W, t0, t1, j_only,
+                         no_object, gen_dev, scratch_dev, counts_dev, nullptr, quality_dev, select_dev, true, annot_dev);
 }
 
 int stcn_metrics_round(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev, const uint8_t *annotated_dev,
@@ -579,6 +587,48 @@ int stcn_metrics_objects_round(void *stream, const uint8_t *masks_dev, int nh, i
                                double *quality_dev, int32_t *select_dev) {
     return metrics_round("stcn_metrics_objects_round", true, stream, masks_dev, nh, nw, lh, lw, gt_dev, annotated_dev, present_dev, k, T, H, W, t0, t1,
                          j_only, no_object, gen_dev, scratch_dev, counts_dev, object_quality_dev, quality_dev, select_dev);
+}
+
+// ---- the simulated user (robot.hip): every argument is checked before any device call ---------------------------------------------------
+static bool robot_args_ok(const char *who, int H, int W, std::initializer_list<const void *> ptrs) {
+    if (H < 1 || W < 1 || (long)H * W > MAX_FRAME_PIXELS) { set_error("%s: bad frame %d x %d (1 <= H * W <= 2^24 pixels)", who, H, W); return false; }
+    for (const void *p : ptrs)
+        if (!p) { set_error("%s: null pointer", who); return false; }
+    return true;
+}
+
+int stcn_robot_scratch(int H, int W, int64_t *bytes) {
+    if (!robot_args_ok("stcn_robot_scratch", H, W, {bytes})) return STCN_E_INVALID;
+    *bytes = (int64_t)robot_scratch_bytes(H, W);
+    return STCN_OK;
+}
+
+int stcn_robot_click(void *stream, const uint8_t *pred_dev, const uint8_t *gt_dev, int H, int W, int mode, int use_iou, double iou, void *scratch_dev,
+                     int32_t *record_dev, uint8_t *component_dev) {
+    const char *who = "stcn_robot_click";
+    if (mode != STCN_ROBOT_INTERACT && mode != STCN_ROBOT_MIDDLE) { set_error("%s: mode %d is neither STCN_ROBOT_INTERACT nor STCN_ROBOT_MIDDLE", who, mode); return STCN_E_INVALID; }
+    const void *unused = who;
+    if (!robot_args_ok(who, H, W, {mode == STCN_ROBOT_MIDDLE ? unused : pred_dev, gt_dev, scratch_dev, record_dev})) return STCN_E_INVALID;
+    if ((uintptr_t)scratch_dev % 8 != 0) { set_error("%s: scratch_dev=%p must be 8-byte aligned", who, scratch_dev); return STCN_E_INVALID; }
+    robot_click_launch(pred_dev, gt_dev, H, W, mode == STCN_ROBOT_MIDDLE, use_iou && iou < 0.1, scratch_dev, record_dev, component_dev, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
+int stcn_robot_bbox(void *stream, const uint8_t *mask_dev, int H, int W, int32_t *record_dev) {
+    if (!robot_args_ok("stcn_robot_bbox", H, W, {mask_dev, record_dev})) return STCN_E_INVALID;
+    robot_bbox_launch(mask_dev, H, W, record_dev, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
+int stcn_robot_best_mask(void *stream, const uint8_t *cand_dev, const uint8_t *target_dev, int M, int H, int W, int32_t *out_dev) {
+    const char *who = "stcn_robot_best_mask";
+    if (M < 1 || M > STCN_ROBOT_MAX_CANDIDATES) { set_error("%s: M = %d outside 1..%d (STCN_ROBOT_MAX_CANDIDATES)", who, M, STCN_ROBOT_MAX_CANDIDATES); return STCN_E_INVALID; }
+    if (!robot_args_ok(who, H, W, {cand_dev, target_dev, out_dev})) return STCN_E_INVALID;
+    robot_best_mask_launch(cand_dev, target_dev, M, H, W, out_dev, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
 }
 
 int stcn_bench_mfma_rate(void *stream, int ms_target, float *tflops, float *ms_out) {

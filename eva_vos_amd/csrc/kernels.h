@@ -308,12 +308,22 @@ void label_counts_launch(const uint8_t *gt, const uint8_t *pred, int k, int Tn, 
 // Pointers at the first of the Tn frames to recount; quality / arg-min over the T_all frames of the clip, t0 = index of that first frame.
 void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *flags, int k,
                         int Tn, int H, int W, int radius, double no_object, uint8_t *gen, void *scratch, int *counts, int T_all,
-                        double *object_quality, double *quality, int *select, hipStream_t s, int t0);
+                        double *object_quality, double *quality, int *select, hipStream_t s, int t0, const uint8_t *annot = nullptr);
 // A trial round of a binary session (stcn_metrics_trial): frames [t0, t1) composed - frame t0 + also counting as annotated, -1: none - and
 // counted into span_gen / bmap / span_counts, then quality [T_all] from span_counts inside the span and the const base counts outside.
 void trial_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *noobj, int also,
                         int T_all, int H, int W, int t0, int t1, int radius, double no_object, const int *base, uint8_t *span_gen, uint8_t *bmap,
                         int *span_counts, double *quality, hipStream_t s);
+
+// ---------------------------------------------------------------- the simulated user (robot.hip; robots/click_robot.py, bbox_robot.py)
+// Masks uint8 [H,W], non-zero = object, H * W <= MAX_FRAME_PIXELS.  All three enqueue only; the number of launches depends on (H, W) and
+// middle_only alone.  robot_scratch_bytes is the one statement of the click call's scratch size (pure host code).
+size_t robot_scratch_bytes(int H, int W);
+// record int32 [STCN_ROBOT_RECORD_INTS]; component: optional uint8 [H,W] OUT; middle_only: pred is not read; two_clicks: the iou < 0.1 branch
+void robot_click_launch(const uint8_t *pred, const uint8_t *gt, int H, int W, int middle_only, int two_clicks, void *scratch, int *record,
+                        uint8_t *component, hipStream_t s);
+void robot_bbox_launch(const uint8_t *mask, int H, int W, int *record, hipStream_t s);                  // record int32 [STCN_ROBOT_BBOX_INTS]
+void robot_best_mask_launch(const uint8_t *cand, const uint8_t *target, int M, int H, int W, int *out, hipStream_t s);      // out int32 [STCN_ROBOT_BEST_INTS]
 
 // ---------------------------------------------------------------- frame distances (frame_select.hip)
 // dist [T][T] fp64 = squared L2 distances between T vectors of K fp32 values, vector t at x + index.v[t] * stride (16-byte aligned: x and

@@ -278,16 +278,19 @@ void label_counts_launch(const uint8_t *gt, const uint8_t *pred, int k, int Tn, 
 // (interactions/eval.py:57-60: annotated frames count with their GT mask).  gen is what util/fq_dataset.py:64-84 saves as a state.
 // Binary masks: non-zero = object; LABELS: label maps of k objects.  `also`: one more frame (of the T composed) that counts as annotated
 // whatever its flag says - the candidate of a trial round, whose flags are the caller's and stay untouched; -1: none.
+// `annot` (typed rounds, else null): the flags are annotation TYPES and a frame of type 2 - annotated with clicks or a box - counts with
+// the annotator's mask annot[t] (interactions/eval.py:61-64); every other non-zero flag is the ground truth as before.
 template <bool LABELS>
 __global__ __launch_bounds__(256) void round_compose_kernel(const uint8_t *__restrict__ masks, int nh, int nw, int lh, int lw,
                                                             const uint8_t *__restrict__ gt, const uint8_t *__restrict__ annotated, int k, int T, int H,
-                                                            int W, uint8_t *__restrict__ gen, int also) {
+                                                            int W, uint8_t *__restrict__ gen, int also, const uint8_t *__restrict__ annot) {
     const long hw = (long)H * W, n = T * hw;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const int t = (int)(i / hw);
         const int rem = (int)(i - t * hw);
         const int y = rem / W, x = rem - y * W;
-        const uint8_t v = annotated[t] || t == also ? gt[i] : masks[((long)t * nh + y + lh) * nw + x + lw];
+        const int flag = annotated[t];
+        const uint8_t v = annot && flag == 2 ? annot[i] : flag || t == also ? gt[i] : masks[((long)t * nh + y + lh) * nw + x + lw];
         gen[i] = LABELS ? (uint8_t)label_of(v, k) : (uint8_t)(v != 0);
     }
 }
@@ -365,11 +368,11 @@ __global__ __launch_bounds__(256) void round_quality_kernel(const int *__restric
 // [k][T_all][6]).
 void round_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, const uint8_t *gt, const uint8_t *annotated, const uint8_t *flags, int k,
                         int Tn, int H, int W, int radius, double no_object, uint8_t *gen, void *scratch, int *counts, int T_all,
-                        double *object_quality, double *quality, int *select, hipStream_t s, int t0) {
+                        double *object_quality, double *quality, int *select, hipStream_t s, int t0, const uint8_t *annot) {
     const long n = (long)Tn * H * W;
     const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(k ? round_compose_kernel<true> : round_compose_kernel<false>, dim3(blocks), dim3(256), 0, s, masks, nh, nw, lh, lw, gt, annotated, k,
-                       Tn, H, W, gen, -1);
+                       Tn, H, W, gen, -1, annot);
     if (k) label_counts_launch(gt, gen, k, Tn, H, W, radius, scratch, counts, T_all, s);
     else jf_counts_launch(gt, gen, Tn, H, W, radius, (uint8_t *)scratch, counts, s);
     hipLaunchKernelGGL(round_quality_kernel, dim3(1), dim3(256), 0, s, counts - (long)t0 * 6, flags, k ? 0 : 1, k ? k : 1, T_all, radius < 0 ? 1 : 0,
@@ -399,7 +402,8 @@ void trial_score_launch(const uint8_t *masks, int nh, int nw, int lh, int lw, co
     if (Tn > 0) {
         const long n = (long)Tn * H * W;
         const unsigned blocks = (unsigned)std::min<long>((n + 255) / 256, 4096);
-        hipLaunchKernelGGL(round_compose_kernel<false>, dim3(blocks), dim3(256), 0, s, masks, nh, nw, lh, lw, gt, annotated, 0, Tn, H, W, span_gen, also);
+        hipLaunchKernelGGL(round_compose_kernel<false>, dim3(blocks), dim3(256), 0, s, masks, nh, nw, lh, lw, gt, annotated, 0, Tn, H, W, span_gen, also,
+                           (const uint8_t *)nullptr);
         jf_counts_launch(gt, span_gen, Tn, H, W, radius, bmap, span_counts, s);
     }
     hipLaunchKernelGGL(trial_quality_kernel, dim3((T_all + 255) / 256), dim3(256), 0, s, base, span_counts, t0, t1, noobj, T_all, radius < 0 ? 1 : 0,

@@ -40,11 +40,14 @@ import torch
 
 from . import metrics, shard
 from .frame_select import farthest_frame
-from .fq_driver import NO_OBJECT, ClipDataset, LaneCores, annotation_session, frame_quality, lane_engine_options, run_lanes
+from .fq_driver import NO_OBJECT, ClipDataset, LaneCores, annotation_session, frame_quality, lane_engine_options, run_lanes, typed_annotation_session
 
 POLICIES = ("oracle_mask", "rand_mask", "qnet_mask", "upper_bound_mask", "l2_mask")
 # QNet takes one binary mask; the upper bound builds on the one-object scorer; the l2 selector needs no mask at all
 MULTI_OBJECT_POLICIES = ("oracle_mask", "rand_mask", "l2_mask")
+# the mixed-annotation policies (interactions/mulitple_annotations.py:104-283): run_typed_policy, with an annotator; one-object sessions
+TYPED_POLICIES = ("rand_type", "rand_rand", "oracle_oracle")
+ANNOTATORS = ("component",)                                   # built in; a real SAM controller is passed through run(..., annotator=...)
 MAX_OBJECTS = 32                                              # STCN_MAX_OBJECTS
 MASK_SECONDS, SKIP_SECONDS = 80, 3            # annotation cost model of interactions/mask.py:33-36
 
@@ -187,9 +190,96 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
     return res
 
 
+def oracle_action(annotator, annotation_types, gt_mask, mivos_mask, im, frame_annots, empty=None):
+    """oracle_action (interactions/mulitple_annotations.py:42-85): every annotation type is tried on the frame and the one with the best
+    reward = (iou - init_iou) / cost is taken; ``>=`` keeps the LAST best, and a box is skipped where one was given before.  Returns
+    (mask, cost, action, logits, clicks, labels, bbox, actions_data)."""
+    best = (None, 1e10, None, None, None, None, None)
+    best_reward = -1e10
+    init_iou = annotator.iou(mivos_mask, gt_mask)
+    data = {"init_iou": init_iou}
+    for ann_type in annotation_types:
+        if ann_type == "bbox" and "bbox" in frame_annots["annotations"]:
+            continue
+        mask, cost, iou, logits, clicks, labels, bbox = annotator.annotate(ann_type, gt_mask, im, mivos_mask, frame_annots, empty=empty)
+        reward = (iou - init_iou) / cost
+        data[ann_type] = dict(iou=iou, cost=cost, reward=reward)
+        if reward >= best_reward:
+            best_reward, best = reward, (mask, cost, ann_type, logits, clicks, labels, bbox)
+    data["selected_action"] = best[2]
+    return best + (data,)
+
+
+def run_typed_policy(policy: str, processor, sample, rounds: int, annotator, annotation_types, metric: str = "j_and_f", rng=None,
+                     stats: dict = None, scorer=None, choose_action=None):
+    """One sample through ``rounds`` rounds of a mixed-annotation policy (``rand_type``, ``rand_rand``, ``oracle_oracle``:
+    interactions/mulitple_annotations.py:161-220, 223-283, 104-158).  ``annotator``: an ``annotate.PromptAnnotator``; ``annotation_types``:
+    'click', 'bbox', 'mask' or '<N>clicks' - exactly one for ``rand_type``, more than one for the others.  The first round is the mask of frame
+    0 at 80 s; later rounds annotate the chosen frame with the policy's action - ``rand_type``: its one type, ``rand_rand``: a random one,
+    ``oracle_oracle``: ``oracle_action`` - and choose the next frame: the arg-min of the round's quality for ``oracle_oracle``, a random frame
+    among those not yet annotated with a mask for the others.  Every draw comes from ``rng`` (the session's own ``random.Random``), so runs are
+    not comparable draw for draw with the reference's global NumPy / ``random`` state.  ``choose_action(frame, gen, frame_annots)`` replaces
+    the policy's action (the hook an ``eva_vos`` agent needs); ``scorer``: another evaluation with ``TypedRoundScorer``'s interface
+    (``metrics.HostTypedScorer``).  Returns the reference's values - ``mu_metrics``, ``annotation_times``, ``annotations_actions``, and
+    ``round_metrics`` / ``annotated_frames`` (the reference returns these two for ``oracle_oracle`` only) - plus ``types`` and
+    ``propagated_frames``."""
+    from .annotate import check_annotation_types
+    assert policy in TYPED_POLICIES, policy
+    types_ = check_annotation_types(annotation_types)
+    if policy == "rand_type" and len(types_) != 1:
+        raise ValueError(f"rand_type takes one annotation type, got {types_}")
+    if policy != "rand_type" and len(types_) < 2:
+        raise ValueError(f"{policy} requires more than one annotation type, got {types_}")
+    if "object_ids" in sample:                                      # a per-video sample (ClipDataset(..., per_video=True))
+        raise ValueError(f"{policy} is a one-object policy: multi-object sessions support {' and '.join(MULTI_OBJECT_POLICIES)}")
+    T = sample["num_frames"]
+    dev = processor.prob.device
+    rng = rng or random
+    gt = sample["gt"][0].to(dev)                                   # [T,1,H,W]
+    images = sample["rgb"][0].to(dev)
+    if scorer is None:
+        scorer = metrics.TypedRoundScorer(gt[:, 0], "j" if metric == "j" else "j_and_f", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
+    empty = scorer.empty_host
+    action_data = []
+
+    def policy_action(frame, gen, frame_annots):
+        g, mivos = gt[frame, 0], gen[frame][None].to(torch.bool)
+        if policy == "oracle_oracle":
+            out = oracle_action(annotator, types_, g, mivos, images[frame], frame_annots, empty=bool(empty[frame]))
+            action_data.append(dict(out[-1], frame_num=frame))
+            return out[:-1]
+        action = types_[0] if policy == "rand_type" else rng.choice(types_)
+        mask, cost, _, logits, clicks, labels, bbox = annotator.annotate(action, g, images[frame], mivos, frame_annots, empty=bool(empty[frame]))
+        return mask, cost, action, logits, clicks, labels, bbox
+
+    def next_frame(worst, types):
+        if policy == "oracle_oracle":
+            return worst
+        left = np.where(types != 1)[0]
+        return int(rng.choice(left.tolist())) if len(left) else None
+
+    stats = {} if stats is None else stats
+    seen = stats.get("propagated_frames", 0)
+    ses = typed_annotation_session(processor, scorer, T, rounds, gt, choose_action or policy_action, next_frame, stats=stats)
+    q = scorer.qualities()
+    per_round = [q[i].copy() for i in range(len(ses["costs"]))]
+    mus = [float(np.mean(row[~empty])) if (~empty).any() else float("nan") for row in per_round]
+    return dict(mu_metrics=mus, annotation_times=ses["costs"], annotations_actions=ses["actions"], round_metrics=per_round,
+                annotated_frames=ses["frames"], frames=ses["frames"], types=ses["types"], action_data=action_data,
+                propagated_frames=stats.get("propagated_frames", 0) - seen)
+
+
+def make_annotator(name: str):
+    """The built-in annotators of the command line: 'component' = ``PromptAnnotator`` over the ``ComponentPredictor`` stand-in."""
+    from .annotate import ComponentPredictor, PromptAnnotator
+    if name != "component":
+        raise ValueError(f"unknown annotator {name!r}: built in are {', '.join(ANNOTATORS)}; pass a PromptAnnotator over a SAM controller to run()")
+    return PromptAnnotator(ComponentPredictor())
+
+
 def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "oracle_mask", rounds: int = 60,
         metric: str = "j_and_f", qnet=None, seed: int = 0, device: str = "cuda", lanes: int = 2, stats: dict = None,
-        multi_object: bool = False, share_frames: bool = True):
+        multi_object: bool = False, share_frames: bool = True, annotator=None, annotation_types=None):
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
     (rows: sample id, round, mu_metric, annotation_time, annotated frame, T, then T per-frame values, NaN-padded).
     `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited), `interactions`, `key_frames_encoded` (frames that
@@ -198,6 +288,10 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     `share_frames` (per-object mode; the protocol and the rows stay the reference's): the sessions of a video's objects run one after the
     other on ONE engine that keeps the clip and its frame features between them (fq_driver.LaneCores) - videos, not samples, are dealt to
     ranks and lanes.  False: a fresh engine and a fresh upload per sample, samples dealt one by one.
+    A policy of TYPED_POLICIES runs ``run_typed_policy`` with ``annotation_types`` and ``annotator`` - a factory of one ``PromptAnnotator`` per
+    lane thread (e.g. ``lambda: PromptAnnotator(sam_controller)``), or the name of a built-in ('component'); per-object mode only.  Its rows
+    carry one more column at the end: the index of the round's action in ``sorted(set(annotation_types) | {'mask'})``, which the CSV names
+    in an ``annotation_actions`` column beside the reference's (eval_annotation_method.py:138-139,185-186).
     `multi_object`: one session per VIDEO with all its objects in one engine.  The rows keep their schema and the sample ids of the per-object
     enumeration, one per (video, object, round), so the outputs of the two modes join on (sample id, round): mu_metric = the mean of that
     object's quality over the frames where it is present, annotation_time = 80 s if the object is present in the annotated frame, else
@@ -209,6 +303,14 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     world = dist.get_world_size() if dist.is_initialized() else 1
     if multi_object and policy not in MULTI_OBJECT_POLICIES:
         raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
+    typed = policy in TYPED_POLICIES
+    if typed:
+        from .annotate import check_annotation_types
+        action_names = sorted(set(check_annotation_types(annotation_types or ())) | {"mask"})
+        if annotator is None:
+            raise ValueError(f"{policy} needs an annotator: 'component' or a factory of PromptAnnotator objects")
+        make = (lambda: make_annotator(annotator)) if isinstance(annotator, str) else annotator
+        lane_annotators = __import__("threading").local()
     ds = ClipDataset(root, imset, per_video=multi_object)
     for v, k, _ in ds.samples if multi_object else ():
         if k > MAX_OBJECTS:
@@ -222,7 +324,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         mine = sorted(shard.lpt_assign([s[2] * (s[1] if multi_object else 1) for s in ds.samples], world)[rank])      # multi-object: frames x objects
     cores = LaneCores(lambda sample: InferenceCore(prop_net, fuse_net, sample["rgb"], sample["num_objects"] if multi_object else 1,
                                                    engine_options=lane_engine_options(lanes)), share_frames)
-    width = 6 + t_max
+    width = 6 + t_max + (1 if typed else 0)
     stats_lock = __import__("threading").Lock()
 
     def work(i, sample):
@@ -231,7 +333,12 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         proc = cores.core_for(sample)
         t_s = time.perf_counter()
         session = {}
-        res = run_policy(policy, proc, sample, rounds, metric, qnet, random.Random(seed * 100003 + i), multi_object=multi_object, stats=session)
+        if typed:
+            if not hasattr(lane_annotators, "a"):
+                lane_annotators.a = make()
+            res = run_typed_policy(policy, proc, sample, rounds, lane_annotators.a, annotation_types, metric, random.Random(seed * 100003 + i), stats=session)
+        else:
+            res = run_policy(policy, proc, sample, rounds, metric, qnet, random.Random(seed * 100003 + i), multi_object=multi_object, stats=session)
         cores.done(proc)
         if stats is not None:
             with stats_lock:
@@ -256,6 +363,8 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
             row = np.full(width, np.nan, np.float32)
             row[:6] = (i, r, mu, sec, res["frames"][r], len(q))
             row[6:6 + len(q)] = q
+            if typed:
+                row[-1] = action_names.index(res["annotations_actions"][r])
             rows.append(row)
         return rows
 
@@ -268,8 +377,11 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         order = np.lexsort((allrows[:, 1], allrows[:, 0]))
         with open(out_csv, "w", newline="") as f:
             wr = csv.writer(f)
-            wr.writerow(["video", "mu_metric", "annotation_time", "round"])
+            wr.writerow(["video", "mu_metric", "annotation_time", "round"] + (["annotation_actions"] if typed else []))
             for row in allrows[order]:
+                if typed:                                          # click costs are fractions of a second
+                    wr.writerow([ds.object_names[int(row[0])], float(row[2]), float(row[3]), int(row[1]), action_names[int(row[-1])]])
+                    continue
                 wr.writerow([ds.object_names[int(row[0])], float(row[2]), int(row[3]), int(row[1])])
     return allrows
 
@@ -278,7 +390,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", required=True)
     ap.add_argument("--imset", required=True)
-    ap.add_argument("--policy", default="oracle_mask", choices=POLICIES)
+    ap.add_argument("--policy", default="oracle_mask", choices=POLICIES + TYPED_POLICIES)
+    ap.add_argument("--annotation-types", nargs="+", default=None, metavar="TYPE", help="the mixed-annotation policies (" + ", ".join(TYPED_POLICIES)
+                    + "): 'click', 'bbox', 'mask' or '<N>clicks'; one type for rand_type, several for the others")
+    ap.add_argument("--annotator", default="component", choices=ANNOTATORS, help="the segmenter behind clicks and boxes: 'component' is a deterministic "
+                    "stand-in that knows the ground truth (NOT a segmenter); a real SAM controller is passed to eval_driver.run(annotator=...)")
     ap.add_argument("--rounds", type=int, default=60)
     ap.add_argument("--lanes", type=int, default=2, help="videos in flight per GPU")
     ap.add_argument("--multi-object", action="store_true", help="one session per video with all its objects in one engine (policies: "
@@ -294,6 +410,11 @@ def main():
     ap.add_argument("--km", type=float, default=None, metavar="SIGMA", help="kernelized memory read: standard deviation (1/16-scale positions) of the Gaussian "
                     "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
     a = ap.parse_args()
+    if a.policy in TYPED_POLICIES:
+        if a.multi_object:
+            ap.error(f"{a.policy} is a one-object policy: --multi-object supports {', '.join(MULTI_OBJECT_POLICIES)}")
+        if not a.annotation_types:
+            ap.error(f"{a.policy} needs --annotation-types")
     import torch.distributed as dist
 
     from . import synth
@@ -316,9 +437,10 @@ def main():
             qnet.load_state_dict(torch.load(a.qnet_weights, map_location="cpu"))
     if qnet is not None:
         qnet = qnet.cuda().eval()
-    out = os.path.join("Experiments", a.db, f"{a.policy}.csv")
+    typed = a.policy in TYPED_POLICIES
+    out = os.path.join("Experiments", a.db, "_".join([a.policy] + (sorted(a.annotation_types) if typed else [])) + ".csv")
     rows = run(a.root, a.imset, out, prop.eval(), fuse.eval(), a.policy, a.rounds, qnet=qnet, lanes=a.lanes, multi_object=a.multi_object,
-               share_frames=not a.no_share_frames)
+               share_frames=not a.no_share_frames, annotator=a.annotator if typed else None, annotation_types=a.annotation_types)
     if not dist.is_initialized() or dist.get_rank() == 0:
         print(f"{len(rows)} rounds -> {out}")
     if dist.is_initialized():

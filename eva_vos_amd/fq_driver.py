@@ -474,6 +474,64 @@ def annotation_session(processor, scorer, T: int, rounds: int, annotate, choose,
     return frames, gens
 
 
+def new_frame_annotations(T: int) -> list:
+    """pf_annots of ``initialize`` (interactions/eval.py:107-115): per frame the actions taken on it and the prompts to continue from."""
+    return [dict(annotations=[], click_labels=None, click_coords=None, bbox=None, sam_logits=None) for _ in range(T)]
+
+
+def typed_annotation_session(processor, scorer, T: int, rounds: int, gt, choose_action, next_frame, stats: dict = None):
+    """The session loop of the mixed-annotation policies (interactions/mulitple_annotations.py:104-283; ``eva_vos``, :307-378, is the same
+    loop with an agent behind ``choose_action``).  Round 1 annotates frame 0 with its mask at 80 s.  Round r > 1 annotates ``frames[-1]``:
+    ``choose_action(frame, gen, frame_annots) -> (mask, cost, action, logits, clicks, labels, bbox)`` is the policy's annotation of it given the
+    masks evaluated last (``gen`` uint8 [T,H,W] on the device); ``store_action_data`` (:88-101): the action 'mask' makes the frame type 1
+    and interacts with the ground truth, every other action makes it type 2, hands the annotator's mask to ``scorer.set_annotation`` and
+    keeps the prompts for a later annotation of the same frame.  The engine propagates (``processor.interact``), ``scorer`` (a
+    metrics.TypedRoundScorer) evaluates, and ``next_frame(worst, types) -> frame or None`` picks the next one - frames REPEAT: a type-2 frame
+    stays selectable until it gets a mask.  Skip rules (:117-123): ``r >= T`` with every frame at quality 1, every frame annotated with a mask
+    (types: none but 1 left), or - after the first round - no frame left that is neither chosen nor without the object (not_avail_frames).
+    ``gt``: [T,1,H,W] on the device.  Returns dict(frames, types, costs, actions): per scored round the annotated frame, its type (1 / 2), the
+    seconds, the action; plus ``pending``: the frame chosen last, or None."""
+    empty = scorer.empty_host
+    valid = set(np.where(~empty)[0].tolist())
+    types = np.zeros(T, np.int64)
+    frames, done_types, costs, actions = [0], [], [], []
+    annots = new_frame_annotations(T)
+    gen, fully, pending = None, False, 0
+    for r in range(1, rounds + 1):
+        if fully or pending is None or (r >= T and gen is not None and float(np.min(scorer.qualities()[-1])) == 1.0):
+            continue
+        if gen is not None and not (valid - set(frames)):
+            continue
+        frame = pending
+        if r > 1:
+            mask, cost, action, logits, clicks, labels, bbox = choose_action(frame, gen, annots[frame])
+        else:
+            mask, cost, action = None, 80, "mask"
+        if action == "mask":
+            types[frame] = 1
+            interaction = gt[frame][None]
+        else:
+            types[frame] = 2
+            interaction = mask.reshape(gt[frame].shape).float()[None]
+            scorer.set_annotation(frame, mask)
+            annots[frame].update(click_labels=labels, click_coords=clicks, bbox=bbox, sam_logits=logits)
+        annots[frame]["annotations"].append(action)
+        processor.interact(interaction, frame, download=False)
+        if stats is not None:
+            stats["propagated_frames"] = stats.get("propagated_frames", 0) + processor.stats()["frames"]
+            stats["interactions"] = stats.get("interactions", 0) + 1
+        done_types.append(int(types[frame]))
+        worst, gen = scorer.score(processor, frames, keep_gen=False, types=done_types)
+        costs.append(cost)
+        actions.append(action)
+        fully = not (types != 1).any()
+        pending = next_frame(worst, types)
+        if pending is not None:
+            frames.append(int(pending))
+    n = len(costs)
+    return dict(frames=frames[:n], types=done_types, costs=costs, actions=actions, pending=pending if len(frames) > n else None)
+
+
 def oracle_rounds(processor, sample, rounds: int = 8, stats: dict = None):
     """The oracle annotation policy of the FQ dataset (interactions/mask.py:113-156): annotate the worst frame by J with its ground-truth
     mask.  `stats` (optional dict, one per caller thread): see annotation_session.

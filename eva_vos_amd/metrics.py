@@ -260,7 +260,13 @@ class RoundScorer:
         self.rounds = 0
         self._scored = frozenset()
 
-    def score(self, processor, annotated_frames, keep_gen: bool = True, incremental: bool = True):
+    def _fill_flags(self, frames, types):
+        """What ``annotated`` on the device says of every frame: 1 = annotated (its ground truth is evaluated)."""
+        if types is not None:
+            raise ValueError("RoundScorer: annotation types are scored by TypedRoundScorer")
+        self.flags_host[sorted(set(frames))] = 1
+
+    def score(self, processor, annotated_frames, keep_gen: bool = True, incremental: bool = True, types=None):
         """Enqueue the evaluation of the round just propagated by ``processor`` and return (selected frame, gen): gen = uint8 [T,H,W] on the
         device (the evaluated masks; a fresh tensor when keep_gen, else a scratch that the next round overwrites).  ``annotated_frames``:
         every frame annotated so far, the one annotated in THIS round last.  ``incremental``: from the second round on only the frames the
@@ -281,7 +287,7 @@ class RoundScorer:
             t1 = min([f for f in others if f > cur] + [self.T])
         with torch.cuda.device(self.dev):
             self.flags_host.zero_()                                   # (the previous round's copy is done: every round ends in a wait)
-            self.flags_host[sorted(set(frames))] = 1
+            self._fill_flags(frames, types)
             self.annotated.copy_(self.flags_host, non_blocking=True)  # T bytes H2D from pinned memory
             prev = getattr(self, "_gen", None)
             if prev is None:
@@ -313,8 +319,8 @@ class RoundScorer:
         import torch
 
         from . import _lib
-        if self.k is not None:
-            raise RuntimeError("RoundScorer.score_trial: trials are scored for one-object (binary) sessions only")
+        if self.k is not None or self._entry != "stcn_metrics_round":
+            raise RuntimeError("RoundScorer.score_trial: trials are scored for one-object (binary) sessions of mask annotations only")
         frames, cand, row = frozenset(int(f) for f in annotated_frames), int(candidate), int(row)
         if self.rounds == 0 or frames != self._scored:
             raise RuntimeError("RoundScorer.score_trial: a trial builds on the round scored last; annotated_frames are not that round's")
@@ -362,3 +368,85 @@ class RoundScorer:
         if self.object_quality is None:
             raise RuntimeError("RoundScorer.object_qualities: a one-object scorer (num_objects=None) has the rows of qualities() only")
         return self.object_quality[: self.rounds].cpu().numpy()
+
+
+def _current_types(T: int, frames, types) -> np.ndarray:
+    """uint8 [T]: the type of every frame after the annotations ``frames`` (with repeats) of the types ``types``: the last one counts."""
+    frames, types = [int(f) for f in frames], [int(t) for t in types]
+    if len(frames) != len(types) or any(t not in (1, 2) for t in types):
+        raise ValueError("one type, 1 (mask) or 2 (clicks / box), per annotated frame")
+    cur = np.zeros(T, np.uint8)
+    for f, t in zip(frames, types):
+        cur[f] = t
+    return cur
+
+
+class TypedRoundScorer(RoundScorer):
+    """``RoundScorer`` for sessions that mix masks with cheaper annotations (``stcn_metrics_round_typed``; interactions/eval.py:57-64): a
+    frame annotated with a mask (type 1) is evaluated with its ground truth, a frame annotated with clicks or a box (type 2) with the
+    annotator's imperfect mask, which ``set_annotation`` stores in a device buffer the scorer owns.  One-object sessions only.
+    ``score(processor, frames, types=...)`` takes every annotation so far, in order and WITH repeats - a type-2 frame stays selectable
+    until it gets a mask - and the type of each; the type of a frame is that of its last annotation.  The frames a round can have changed are
+    those between the annotated neighbours of the frame just (re)annotated, plus that frame (its evaluated mask changes with its type)."""
+
+    def __init__(self, gt_thw, metric: str = "j", max_rounds: int = 64, no_object: float = 20.0):
+        import torch
+        super().__init__(gt_thw, metric, max_rounds, no_object)
+        self.annot = torch.zeros((self.T, self.H, self.W), dtype=torch.uint8, device=self.dev)
+        self._entry = "stcn_metrics_round_typed"
+        from . import _lib
+        self._enqueue = getattr(_lib.lib(), self._entry)
+        self._which = (_ptr(self.annot), _ptr(self.noobj))
+
+    def set_annotation(self, frame: int, mask) -> None:
+        """The annotator's mask of a type-2 frame ([H,W], any dtype, on the scorer's device; non-zero = object): a device copy, no sync."""
+        import torch
+        m = mask.reshape(self.H, self.W)
+        self.annot[int(frame)].copy_(m if m.dtype == torch.uint8 else (m > 0.5 if m.is_floating_point() else m != 0))
+
+    def _fill_flags(self, frames, types):
+        if types is None:
+            raise ValueError("TypedRoundScorer.score: give the type of every annotation (types=...)")
+        self.flags_host.copy_(__import__("torch").from_numpy(_current_types(self.T, frames, types)))
+
+
+class HostTypedScorer:
+    """The typed evaluation restated on the host - the yardstick of ``TypedRoundScorer`` and the scoring of the host route that
+    tools/click_robot_cost.py measures against: every round downloads the engine's masks, composes the evaluated masks in NumPy
+    (interactions/eval.py:57-64), counts with ``label_counts`` (NumPy / SciPy) and scores with ``_scores_from_counts``.  Same interface,
+    same values to the bit, every frame recounted in every round."""
+
+    def __init__(self, gt_thw, metric: str = "j", max_rounds: int = 64, no_object: float = 20.0):
+        g = gt_thw.detach().cpu().numpy()
+        self.gt = (g > 0.5 if g.dtype.kind == "f" else g != 0).astype(np.uint8)
+        self.T, self.H, self.W = self.gt.shape
+        self.dev = gt_thw.device
+        self.metric, self.no_object = metric, float(no_object)
+        self.empty_host = self.gt.reshape(self.T, -1).sum(1) == 0
+        self.annot = np.zeros_like(self.gt)
+        self.rows, self.gens = [], []
+        self.rounds = 0
+
+    def set_annotation(self, frame: int, mask) -> None:
+        m = mask.detach().cpu().numpy() if hasattr(mask, "detach") else np.asarray(mask)
+        self.annot[int(frame)] = (m.reshape(self.H, self.W) != 0)
+
+    def score(self, processor, annotated_frames, keep_gen: bool = True, incremental: bool = True, types=None):
+        import torch
+        cur = _current_types(self.T, annotated_frames, types)
+        lw, uw, lh, uh = processor.pad
+        seg = (processor.masks[:, 0, lh:processor.nh - uh, lw:processor.nw - uw] > 0).cpu().numpy().astype(np.uint8)
+        gen = np.where(cur[:, None, None] == 1, self.gt, np.where(cur[:, None, None] == 2, self.annot, seg)).astype(np.uint8)
+        c = label_counts(self.gt, gen, 1)[0]
+        if self.metric == "j":
+            q = np.array([0.0 if u == 0 else i / u for i, u in c[:, :2].tolist()], np.float64)
+        else:
+            q = _scores_from_counts(c)[:, 2].copy()
+        q[self.empty_host] = self.no_object
+        self.rows.append(q)
+        self.counts = c
+        self.rounds += 1
+        return int(np.argmin(q)), torch.from_numpy(gen).to(self.dev)
+
+    def qualities(self):
+        return np.stack(self.rows) if self.rows else np.zeros((0, self.T), np.float64)

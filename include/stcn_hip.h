@@ -570,6 +570,68 @@ int stcn_metrics_objects_round(void *stream, const uint8_t *masks_dev, int nh, i
                                double no_object, uint8_t *gen_dev, void *scratch_dev, int32_t *counts_dev, double *object_quality_dev,
                                double *quality_dev, int32_t *select_dev);
 
+/* ---- typed rounds: sessions that mix masks with cheaper annotations (clicks, a box) ------------------------------------------
+ * stcn_metrics_round with an annotation TYPE per frame in the place of the annotated flag (interactions/eval.py:57-64: a frame annotated
+ * with a mask, type 1, is evaluated with its ground truth; one annotated with clicks or a box, type 2, with the annotator's imperfect mask):
+ *   type_dev  : uint8 [T] - 0 = the engine's mask, 1 = ground truth, 2 = annotator mask (any other non-zero value counts as 1)
+ *   annot_dev : uint8 [T,H,W], non-zero = object - the current annotator mask of every type-2 frame; other frames are not read
+ * Binary masks only (the reference's typed policies are one-object).  Counts, quality, arg-min and the [t0, t1) contract are those of
+ * stcn_metrics_round; without a type-2 frame the outputs are its outputs, bit for bit. */
+int stcn_metrics_round_typed(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev, const uint8_t *type_dev,
+                             const uint8_t *annot_dev, const uint8_t *noobj_dev, int T, int H, int W, int t0, int t1, int j_only, double no_object,
+                             uint8_t *gen_dev, uint8_t *scratch_dev, int32_t *counts_dev, double *quality_dev, int32_t *select_dev);
+
+/* ---- the simulated user on the device (robots/click_robot.py, robots/bbox_robot.py, annotator/annotator.py:38-57) ---------------
+ * Masks are uint8 [H,W], non-zero = object, 1 <= H * W <= 2^24 (the engine's largest padded frame).  Every call enqueues on `stream`
+ * without a sync; null pointers (other than those marked optional) and H * W outside that range return STCN_E_INVALID before any device call.
+ *
+ * The click record, int32 [STCN_ROBOT_RECORD_INTS]: */
+#define STCN_ROBOT_N_CLICKS   0    /* 0 (no object to click on), 1 or 2 */
+#define STCN_ROBOT_X0         1    /* first click (x, y, label): label 0 = negative click, 1 = positive click */
+#define STCN_ROBOT_Y0         2
+#define STCN_ROBOT_LABEL0     3
+#define STCN_ROBOT_X1         4    /* second click: only the iou < 0.1 branch gives one */
+#define STCN_ROBOT_Y1         5
+#define STCN_ROBOT_LABEL1     6
+#define STCN_ROBOT_CLASS      7    /* the clicked region: 0 = none (middle click), 1 = false positive, 2 = false negative */
+#define STCN_ROBOT_FP_SIZE    8    /* pixels of the largest false-positive / false-negative component (0: there is none) */
+#define STCN_ROBOT_FN_SIZE    9
+#define STCN_ROBOT_FP_COUNT   10   /* false-positive / false-negative components */
+#define STCN_ROBOT_FN_COUNT   11
+#define STCN_ROBOT_MOVED      12   /* 1: a positive click of the record fell outside the object and was moved to its nearest pixel */
+#define STCN_ROBOT_RECORD_INTS 16  /* the rest is zero */
+#define STCN_ROBOT_INTERACT   0    /* mode */
+#define STCN_ROBOT_MIDDLE     1
+/* Bytes of scratch_dev for an H x W frame (the one statement of its size).  Works without a GPU. */
+int stcn_robot_scratch(int H, int W, int64_t *bytes);
+/* ClickRobot.interact (robots/click_robot.py:14-75) / ClickRobot.middle_click (:78-99) of one mask pair:
+ *   mode STCN_ROBOT_INTERACT: 8-connected components of the false-positive (pred && !gt) and of the false-negative (!pred && gt) region
+ *     (:22-23,39-40, skimage.measure.label connectivity=2); per region the largest component, on equal sizes the one whose first pixel comes
+ *     first in raster order (:27-28,43-44); its centroid (int(mean x), int(mean y)), the means in correctly rounded fp64 (:31-33,47-49); the
+ *     positive click moves to the nearest object pixel - smallest squared distance, first in raster order - when it is not on the object
+ *     (:51-55); the larger of the two components is clicked, the false positive on a tie (:63-70); use_iou != 0 and iou < 0.1 with a negative
+ *     click chosen and a false negative present: both clicks, labels (0, 1) (:71-74); no error at all: the middle click (:64-65).
+ *   mode STCN_ROBOT_MIDDLE: pred_dev may be NULL; the medians of the rows and of the columns of the object pixels (an even count: the mean of
+ *     the two middle values), int(), with the same nearest-pixel fallback (:83-93).  An empty gt gives a record with 0 clicks (the reference
+ *     raises there).
+ *   record_dev    : int32 [STCN_ROBOT_RECORD_INTS] OUT
+ *   component_dev : optional uint8 [H,W] OUT - 1 on the pixels of the clicked component (STCN_ROBOT_CLASS), all zero for a middle click
+ * The object is `gt != 0` everywhere (the reference tests `gt == 1` in the fallback; its masks are 0 / 1). */
+int stcn_robot_click(void *stream, const uint8_t *pred_dev, const uint8_t *gt_dev, int H, int W, int mode, int use_iou, double iou,
+                     void *scratch_dev, int32_t *record_dev, uint8_t *component_dev);
+/* BboxRobot.interact (robots/bbox_robot.py:11-16: torchvision.ops.masks_to_boxes of one mask): record_dev int32 [STCN_ROBOT_BBOX_INTS] OUT =
+ * { 1, x1, y1, x2, y2 } - the smallest and largest x and y of the non-zero pixels - or { 0, 0, 0, 0, 0 } for an empty mask ("no box"). */
+#define STCN_ROBOT_BBOX_INTS  5
+int stcn_robot_bbox(void *stream, const uint8_t *mask_dev, int H, int W, int32_t *record_dev);
+/* Annotator.best_sam_mask (annotator/annotator.py:38-57) with compute_iou (interactions/metrics.py:9-19): M candidates (1 <= M <=
+ * STCN_ROBOT_MAX_CANDIDATES) cand_dev uint8 [M,H,W] against target_dev uint8 [H,W]:
+ *   out_dev int32 [STCN_ROBOT_BEST_INTS] OUT = { selection, the bits of its fp32 IoU, then M pairs (intersection, union) }
+ * IoU = (float(intersection) + 1e-6f) / (float(union) + 1e-6f) in fp32; the selection is the first candidate whose IoU is strictly above
+ * the running maximum, which starts at 0 (-1 and 0.0 when there is none).  The caller downloads the first 8 bytes. */
+#define STCN_ROBOT_MAX_CANDIDATES 8
+#define STCN_ROBOT_BEST_INTS  (2 + 2 * STCN_ROBOT_MAX_CANDIDATES)
+int stcn_robot_best_mask(void *stream, const uint8_t *cand_dev, const uint8_t *target_dev, int M, int H, int W, int32_t *out_dev);
+
 #ifdef __cplusplus
 }
 #endif
