@@ -89,6 +89,17 @@ class PromptAnnotator:
             self.predictor.set_target(gt_mask)
         self.predictor.set_image(im)
 
+    def image_embedding(self, im, gt_mask):
+        """The segmenter's embedding of the frame, the agent's first input (rl_agent_annotate, interactions/mulitple_annotations.py:293-294):
+        ``set_image`` as above, then ``get_image_embedding()`` of the predictor or of ``predictor.predictor`` - where the reference's
+        ``SAMController`` keeps SAM's own predictor (sam/sam_controller.py) -> [1,256,64,64]."""
+        for p in (self.predictor, getattr(self.predictor, "predictor", None)):
+            if hasattr(p, "get_image_embedding"):
+                self.set_image(im, gt_mask)
+                return p.get_image_embedding()
+        raise ValueError(f"eva_vos needs the image embedding its agent reads: {type(self.predictor).__name__} offers no get_image_embedding(), "
+                         "neither itself nor through a .predictor attribute (SAMController, ComponentPredictor do)")
+
     def create_similar_samlogits(self, pred_mask):
         """annotator.py:60-107: a segmenter cannot be prompted with the propagated mask, so make it produce a similar one: a middle click,
         then up to 20 corrective clicks, until the best candidate's IoU with ``pred_mask`` is above 0.8; (None,) * 4 when it never is."""
@@ -206,8 +217,11 @@ class ComponentPredictor:
 
     Like SAM's predictor it works on the host and uploads its masks: prompts are small host arrays, logits stay host arrays."""
 
+    EMBED_SEED = 17                                     # Philox key of the fixed 256 x 3 matrix of get_image_embedding
+
     def __init__(self):
         self.gt = None
+        self.image = None
         self.embedded = False
         self.device = None
 
@@ -218,9 +232,24 @@ class ComponentPredictor:
     def set_image(self, image):
         assert self.gt is not None, "ComponentPredictor: set_target(gt) before set_image"
         self.embedded = True
+        self.image = image
 
     def reset_image(self):
-        self.embedded, self.gt = False, None
+        self.embedded, self.gt, self.image = False, None, None
+
+    def get_image_embedding(self):
+        """A deterministic stand-in of the SHAPE of SAM's image embedding, [1,256,64,64] fp32 on the target's device - NOT an embedding of
+        anything learned: the 64 x 64 area means of the uint8 image handed to ``set_image``, scaled to 0..1, times a fixed 256 x 3 matrix
+        drawn from a Philox stream.  Equal images give equal values, different images different ones; that is all an agent with recipe
+        weights needs."""
+        import torch
+        import torch.nn.functional as F
+        assert self.embedded and self.image is not None, "get_image_embedding is called before set_image"
+        img = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.uint8)).permute(2, 0, 1)[None].float() / 255
+        means = F.adaptive_avg_pool2d(img, 64)[0]                                      # [3,64,64]
+        m = np.random.Generator(np.random.Philox(key=[self.EMBED_SEED, 256])).normal(0, 1, (256, 3)).astype(np.float32)
+        emb = torch.einsum("kc,chw->khw", torch.from_numpy(m), means)[None].contiguous()
+        return emb.to(self.device) if self.device is not None else emb
 
     def predict(self, click_coords=None, click_labels=None, bbox=None, mask_input=None, multimask_output=True):
         import torch

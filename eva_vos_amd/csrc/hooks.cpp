@@ -631,6 +631,24 @@ int stcn_robot_best_mask(void *stream, const uint8_t *cand_dev, const uint8_t *t
     return STCN_OK;
 }
 
+// ---- masks as network input (resize.hip): every argument is checked before any device call ---------------------------------------------
+int stcn_masks_resize_nearest(void *stream, const uint8_t *src, int T, int H, int W, const int32_t *frames_dev, int n, int out_h, int out_w, int channels,
+                              float *out) {
+    const char *who = "stcn_masks_resize_nearest";
+    if (!src || !out) { set_error("%s: null pointer (%s)", who, !src ? "src" : "out"); return STCN_E_INVALID; }
+    if (T < 1 || H < 1 || W < 1) { set_error("%s: bad source [%d, %d, %d]: every size is at least 1", who, T, H, W); return STCN_E_INVALID; }
+    if (out_h < 1 || out_w < 1 || channels < 1 || (long)out_h * out_w > MAX_FRAME_PIXELS) {
+        set_error("%s: bad output [n, %d, %d, %d]: every size is at least 1, out_h * out_w at most 2^24", who, channels, out_h, out_w);
+        return STCN_E_INVALID;
+    }
+    if (frames_dev && n <= 0) { set_error("%s: frames_dev is given with n = %d (at least 1 frame)", who, n); return STCN_E_INVALID; }
+    if (!frames_dev && (n <= 0 || n > T)) { set_error("%s: n = %d without frames_dev means the first n of the T = %d frames (1 <= n <= T)", who, n, T); return STCN_E_INVALID; }
+    if (n > 65535) { set_error("%s: n = %d frames in one call, at most 65535", who, n); return STCN_E_INVALID; }
+    masks_resize_nearest_launch(src, T, H, W, frames_dev, n, out_h, out_w, channels, out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
 int stcn_bench_mfma_rate(void *stream, int ms_target, float *tflops, float *ms_out) {
     if (!tflops || ms_target < 1 || ms_target > 2000) { set_error("stcn_bench_mfma_rate: bad arguments"); return STCN_E_INVALID; }
     hipStream_t s = (hipStream_t)stream;

@@ -325,6 +325,13 @@ void robot_click_launch(const uint8_t *pred, const uint8_t *gt, int H, int W, in
 void robot_bbox_launch(const uint8_t *mask, int H, int W, int *record, hipStream_t s);                  // record int32 [STCN_ROBOT_BBOX_INTS]
 void robot_best_mask_launch(const uint8_t *cand, const uint8_t *target, int M, int H, int W, int *out, hipStream_t s);      // out int32 [STCN_ROBOT_BEST_INTS]
 
+// ---------------------------------------------------------------- masks as network input (resize.hip)
+// src uint8 [T,H,W] -> out fp32 [n,channels,out_h,out_w]: nearest (torch's rule in fp32), the byte's value as a float, every channel the same
+// plane.  frames: device int32 [n] or nullptr = frames 0..n-1; an index outside [0,T) is not read, its planes become NaN.  out_h * out_w <=
+// MAX_FRAME_PIXELS, n <= 65535 (checked by the caller).  Enqueues one launch.
+void masks_resize_nearest_launch(const uint8_t *src, int T, int H, int W, const int *frames, int n, int out_h, int out_w, int channels, float *out,
+                                 hipStream_t s);
+
 // ---------------------------------------------------------------- frame distances (frame_select.hip)
 // dist [T][T] fp64 = squared L2 distances between T vectors of K fp32 values, vector t at x + index.v[t] * stride (16-byte aligned: x and
 // stride multiples of 4 floats, K % 4 == 0, K >= 4, 1 <= T <= FRAME_GRAM_MAX_T).  The Gram matrix is accumulated in fp64 on the matrix cores

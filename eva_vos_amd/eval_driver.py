@@ -4,8 +4,9 @@ Own counterpart of the reference driver ``eval_annotation_method.py:118-190`` fo
 ground-truth masks - ``oracle_mask``, ``rand_mask``, ``qnet_mask``, ``upper_bound_mask``, ``l2_mask`` (``interactions/mask.py:10-39,
 42-71,74-103,196-227,159-193``) - with their helpers ``initialize`` / ``not_avail_frames`` / ``eval_processor_metric``
 (``interactions/eval.py:27-117``) and the frame selectors of ``interactions/policies.py``.  The click / bbox policies
-and ``eva_vos`` itself additionally need SAM (``segment_anything``) and the PPO agent, which north_star leaves on stock
-PyTorch-ROCm and which are not installed offline; they call the same ``InferenceCore.interact`` boundary.
+additionally need SAM (``segment_anything``), which north_star leaves on stock PyTorch-ROCm and which is not installed offline; the
+mixed-annotation policies (``run_typed_policy``) and ``eva_vos`` itself (``run_eva_vos``: the QNet picks the frame, the actor-critic agent
+the annotation type) therefore run over any predictor with the SAM controller's signature, the ``ComponentPredictor`` stand-in included.
 
 Differences by design:
 
@@ -47,6 +48,8 @@ POLICIES = ("oracle_mask", "rand_mask", "qnet_mask", "upper_bound_mask", "l2_mas
 MULTI_OBJECT_POLICIES = ("oracle_mask", "rand_mask", "l2_mask")
 # the mixed-annotation policies (interactions/mulitple_annotations.py:104-283): run_typed_policy, with an annotator; one-object sessions
 TYPED_POLICIES = ("rand_type", "rand_rand", "oracle_oracle")
+# eva_vos (interactions/mulitple_annotations.py:286-378): run_eva_vos, with an annotator, the QNet and the agent; one-object sessions
+AGENT_POLICIES = ("eva_vos",)
 ANNOTATORS = ("component",)                                   # built in; a real SAM controller is passed through run(..., annotator=...)
 MAX_OBJECTS = 32                                              # STCN_MAX_OBJECTS
 MASK_SECONDS, SKIP_SECONDS = 80, 3            # annotation cost model of interactions/mask.py:33-36
@@ -269,6 +272,65 @@ def run_typed_policy(policy: str, processor, sample, rounds: int, annotator, ann
                 propagated_frames=stats.get("propagated_frames", 0) - seen)
 
 
+def run_eva_vos(processor, sample, rounds: int, annotator, qnet, agent, metric: str = "j_and_f", rng=None, stats: dict = None, scorer=None,
+                selector=None):
+    """One sample through ``rounds`` rounds of ``eva_vos`` (interactions/mulitple_annotations.py:307-378): the first round is the mask of frame
+    0 at 80 s; every later round the AGENT chooses how the pending frame is annotated (``rl_agent_annotate``, :286-304) and the QNET which
+    frame comes next (:356-369).  ``annotator``: an ``annotate.PromptAnnotator`` whose predictor gives an image embedding; ``qnet``: a
+    ``QualityNet`` in eval mode; ``agent``: an ``agent.PPOAgent``; ``rng``: the session's ``torch.Generator`` the agent's draws come from (None:
+    torch's global one) - runs are reproducible under it and, as for the other typed policies, not comparable draw for draw with the reference.
+    ``selector``: the video's ``qnet.QNetSelector`` when the caller keeps one (the sessions of a video's objects), else one is made from
+    ``sample['rgb']``; its ``masks_to_input`` (``agent.masks_to_224`` by default) also builds the agent's mask input; ``scorer``: another evaluation with ``TypedRoundScorer``'s interface (``metrics.HostTypedScorer``).
+    The annotation types are the reference's hard-coded ``['3clicks', 'mask'][action]``, plus 'no_object' (3 s, value 0, no agent call) on a frame
+    without the object.  Returns the reference's values - ``mu_metrics``, ``annotation_times``, ``rl_values`` (the first entry is -2, :316),
+    ``annotations_actions``, ``round_metrics``, ``annotated_frames`` - plus ``frames``, ``types`` and ``propagated_frames``."""
+    from .agent import AVAIL_ACTIONS, masks_to_224
+    from .annotate import ANNOTATION_COSTS
+    if "object_ids" in sample:                                      # a per-video sample (ClipDataset(..., per_video=True))
+        raise ValueError(f"eva_vos is a one-object policy: multi-object sessions support {' and '.join(MULTI_OBJECT_POLICIES)}")
+    T = sample["num_frames"]
+    dev = processor.prob.device
+    gt = sample["gt"][0].to(dev)                                   # [T,1,H,W]
+    images = sample["rgb"][0].to(dev)
+    if scorer is None:
+        scorer = metrics.TypedRoundScorer(gt[:, 0], "j" if metric == "j" else "j_and_f", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
+    if selector is None:
+        from .qnet import QNetSelector
+        selector = QNetSelector(qnet, images)
+    empty = scorer.empty_host
+    rl_values = [-2]
+    to_input = getattr(selector, "masks_to_input", masks_to_224)     # the selector's route from masks to network input serves the agent too
+
+    def choose_action(frame, gen, frame_annots):
+        g = gt[frame, 0]
+        if empty[frame]:                                            # frame_annots['metric'] == 20 (:290-291): nothing to ask the agent
+            rl_values.append(0)
+            return g, ANNOTATION_COSTS["no_object"], "no_object", None, None, None, None
+        embedding = annotator.image_embedding(images[frame], g)
+        action, value = agent.act(embedding, to_input(gen, [frame]), generator=rng)
+        ann_type = AVAIL_ACTIONS[action]
+        mask, cost, _, logits, clicks, labels, bbox = annotator.annotate(ann_type, g, images[frame], gen[frame][None].to(torch.bool), frame_annots, empty=False)
+        rl_values.append(float(value.squeeze().item()))
+        return mask, cost, ann_type, logits, clicks, labels, bbox
+
+    def select(worst, types, gen, frames):
+        if len(frames) < T:                                         # round r = len(frames): r < T
+            return selector.select(gen, frames)
+        # from r >= T on the reference hands the frames NOT yet annotated with a mask to qnet_frame_selection as its "interacted" set
+        # (:361-367) - the selection is then the frame farthest from those, which may well be one that has its mask.  Kept as it is.
+        left = np.where(types != 1)[0]
+        return selector.select(gen, left.tolist()) if len(left) else None
+
+    stats = {} if stats is None else stats
+    seen = stats.get("propagated_frames", 0)
+    ses = typed_annotation_session(processor, scorer, T, rounds, gt, choose_action, None, stats=stats, select=select)
+    q = scorer.qualities()
+    per_round = [q[i].copy() for i in range(len(ses["costs"]))]
+    mus = [float(np.mean(row[~empty])) if (~empty).any() else float("nan") for row in per_round]
+    return dict(mu_metrics=mus, annotation_times=ses["costs"], rl_values=rl_values, annotations_actions=ses["actions"], round_metrics=per_round,
+                annotated_frames=ses["frames"], frames=ses["frames"], types=ses["types"], propagated_frames=stats.get("propagated_frames", 0) - seen)
+
+
 def make_annotator(name: str):
     """The built-in annotators of the command line: 'component' = ``PromptAnnotator`` over the ``ComponentPredictor`` stand-in."""
     from .annotate import ComponentPredictor, PromptAnnotator
@@ -279,7 +341,7 @@ def make_annotator(name: str):
 
 def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "oracle_mask", rounds: int = 60,
         metric: str = "j_and_f", qnet=None, seed: int = 0, device: str = "cuda", lanes: int = 2, stats: dict = None,
-        multi_object: bool = False, share_frames: bool = True, annotator=None, annotation_types=None):
+        multi_object: bool = False, share_frames: bool = True, annotator=None, annotation_types=None, agent=None):
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
     (rows: sample id, round, mu_metric, annotation_time, annotated frame, T, then T per-frame values, NaN-padded).
     `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited), `interactions`, `key_frames_encoded` (frames that
@@ -292,6 +354,11 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     lane thread (e.g. ``lambda: PromptAnnotator(sam_controller)``), or the name of a built-in ('component'); per-object mode only.  Its rows
     carry one more column at the end: the index of the round's action in ``sorted(set(annotation_types) | {'mask'})``, which the CSV names
     in an ``annotation_actions`` column beside the reference's (eval_annotation_method.py:138-139,185-186).
+    ``eva_vos`` (AGENT_POLICIES) runs ``run_eva_vos`` with ``qnet`` (eval mode), ``agent`` (an ``agent.PPOAgent``) - both shared by the lanes - and
+    ``annotator`` as above; each session draws from its own ``torch.Generator`` seeded ``seed * 100003 + sample``, the sessions of a video's
+    objects share one ``QNetSelector`` when they share an engine; per-object mode only.  Its rows carry two more columns: the action's index in
+    ``sorted({'3clicks', 'mask', 'no_object'})`` and, last, the agent's value (``rl_values``, -2 for the first round); CSV columns
+    ``video, mu_metric, annotation_time, round, rl_values, annotation_actions``.
     `multi_object`: one session per VIDEO with all its objects in one engine.  The rows keep their schema and the sample ids of the per-object
     enumeration, one per (video, object, round), so the outputs of the two modes join on (sample id, round): mu_metric = the mean of that
     object's quality over the frames where it is present, annotation_time = 80 s if the object is present in the annotated frame, else
@@ -304,11 +371,20 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     if multi_object and policy not in MULTI_OBJECT_POLICIES:
         raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
     typed = policy in TYPED_POLICIES
+    agent_policy = policy in AGENT_POLICIES
+    if agent_policy:
+        for name, given in (("qnet", qnet), ("agent", agent), ("annotator", annotator)):
+            if given is None:
+                raise ValueError(f"{policy} needs {name}=...: a QualityNet in eval mode, an agent.PPOAgent and an annotator ('component' or a factory "
+                                 "of PromptAnnotator objects)")
+        action_names = sorted({"3clicks", "mask", "no_object"})
+        lane_selectors = __import__("threading").local()
     if typed:
         from .annotate import check_annotation_types
         action_names = sorted(set(check_annotation_types(annotation_types or ())) | {"mask"})
         if annotator is None:
             raise ValueError(f"{policy} needs an annotator: 'component' or a factory of PromptAnnotator objects")
+    if typed or agent_policy:
         make = (lambda: make_annotator(annotator)) if isinstance(annotator, str) else annotator
         lane_annotators = __import__("threading").local()
     ds = ClipDataset(root, imset, per_video=multi_object)
@@ -324,7 +400,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         mine = sorted(shard.lpt_assign([s[2] * (s[1] if multi_object else 1) for s in ds.samples], world)[rank])      # multi-object: frames x objects
     cores = LaneCores(lambda sample: InferenceCore(prop_net, fuse_net, sample["rgb"], sample["num_objects"] if multi_object else 1,
                                                    engine_options=lane_engine_options(lanes)), share_frames)
-    width = 6 + t_max + (1 if typed else 0)
+    width = 6 + t_max + (1 if typed else 2 if agent_policy else 0)
     stats_lock = __import__("threading").Lock()
 
     def work(i, sample):
@@ -333,9 +409,18 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         proc = cores.core_for(sample)
         t_s = time.perf_counter()
         session = {}
-        if typed:
-            if not hasattr(lane_annotators, "a"):
-                lane_annotators.a = make()
+        if (typed or agent_policy) and not hasattr(lane_annotators, "a"):
+            lane_annotators.a = make()
+        if agent_policy:
+            selector = None
+            if share_frames:                                        # the sessions of a video's objects: one clip, one pass of the QNet's frame branch
+                if getattr(lane_selectors, "video", None) != sample["video"]:
+                    from .qnet import QNetSelector
+                    lane_selectors.video, lane_selectors.s = sample["video"], QNetSelector(qnet, sample["rgb"][0])
+                selector = lane_selectors.s
+            res = run_eva_vos(proc, sample, rounds, lane_annotators.a, qnet, agent, metric, torch.Generator().manual_seed(seed * 100003 + i),
+                              stats=session, selector=selector)
+        elif typed:
             res = run_typed_policy(policy, proc, sample, rounds, lane_annotators.a, annotation_types, metric, random.Random(seed * 100003 + i), stats=session)
         else:
             res = run_policy(policy, proc, sample, rounds, metric, qnet, random.Random(seed * 100003 + i), multi_object=multi_object, stats=session)
@@ -365,10 +450,17 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
             row[6:6 + len(q)] = q
             if typed:
                 row[-1] = action_names.index(res["annotations_actions"][r])
+            if agent_policy:
+                row[-2:] = (action_names.index(res["annotations_actions"][r]), res["rl_values"][r])
             rows.append(row)
         return rows
 
-    rows = run_lanes(root, imset, mine, lanes, work, device, stats, per_video=multi_object, share_frames=share_frames, lane_done=cores.release)
+    def lane_done():
+        cores.release()
+        if agent_policy:
+            lane_selectors.video = lane_selectors.s = None
+
+    rows = run_lanes(root, imset, mine, lanes, work, device, stats, per_video=multi_object, share_frames=share_frames, lane_done=lane_done)
     if stats is not None:
         cores.add_to(stats)
     allrows = shard.gather_rows(np.stack(rows) if rows else np.zeros((0, width), np.float32), width)
@@ -377,8 +469,12 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         order = np.lexsort((allrows[:, 1], allrows[:, 0]))
         with open(out_csv, "w", newline="") as f:
             wr = csv.writer(f)
-            wr.writerow(["video", "mu_metric", "annotation_time", "round"] + (["annotation_actions"] if typed else []))
+            wr.writerow(["video", "mu_metric", "annotation_time", "round"] + (["rl_values"] if agent_policy else [])
+                        + (["annotation_actions"] if typed or agent_policy else []))
             for row in allrows[order]:
+                if agent_policy:
+                    wr.writerow([ds.object_names[int(row[0])], float(row[2]), float(row[3]), int(row[1]), float(row[-1]), action_names[int(row[-2])]])
+                    continue
                 if typed:                                          # click costs are fractions of a second
                     wr.writerow([ds.object_names[int(row[0])], float(row[2]), float(row[3]), int(row[1]), action_names[int(row[-1])]])
                     continue
@@ -390,7 +486,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", required=True)
     ap.add_argument("--imset", required=True)
-    ap.add_argument("--policy", default="oracle_mask", choices=POLICIES + TYPED_POLICIES)
+    ap.add_argument("--policy", default="oracle_mask", choices=POLICIES + TYPED_POLICIES + AGENT_POLICIES)
     ap.add_argument("--annotation-types", nargs="+", default=None, metavar="TYPE", help="the mixed-annotation policies (" + ", ".join(TYPED_POLICIES)
                     + "): 'click', 'bbox', 'mask' or '<N>clicks'; one type for rand_type, several for the others")
     ap.add_argument("--annotator", default="component", choices=ANNOTATORS, help="the segmenter behind clicks and boxes: 'component' is a deterministic "
@@ -405,11 +501,14 @@ def main():
     ap.add_argument("--prop-weights", default="./model_weights/mivos/stcn.pth")
     ap.add_argument("--fusion-weights", default="./model_weights/mivos/fusion.pth")
     ap.add_argument("--qnet-weights", default="./model_weights/qnet/qnet.pth")
+    ap.add_argument("--agent-weights", default="./model_weights/rl_agent/model.pth", help="eva_vos: the actor-critic agent's checkpoint")
     ap.add_argument("--synthetic-weights", action="store_true", help="use the deterministic recipe (no checkpoints)")
     ap.add_argument("--top-k", type=int, default=50, help="rows of the memory bank each query reads, 1..50 (PropagationNetwork(top_k=...): 20 for STCN checkpoints, 50 for MiVOS)")
     ap.add_argument("--km", type=float, default=None, metavar="SIGMA", help="kernelized memory read: standard deviation (1/16-scale positions) of the Gaussian "
                     "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
     a = ap.parse_args()
+    if a.policy in AGENT_POLICIES and a.annotation_types:
+        ap.error(f"{a.policy} takes no --annotation-types: its agent chooses between '3clicks' and 'mask', as the reference's")
     if a.policy in TYPED_POLICIES:
         if a.multi_object:
             ap.error(f"{a.policy} is a one-object policy: --multi-object supports {', '.join(MULTI_OBJECT_POLICIES)}")
@@ -421,8 +520,8 @@ def main():
     from .params import FusionNet, PropagationNetwork
     torch.set_grad_enabled(False)
     shard.init_from_env()                                  # one process per GPU; RCCL unless STCN_DIST_BACKEND says otherwise
-    prop, fuse, qnet = PropagationNetwork(top_k=a.top_k, km=a.km), FusionNet(), None
-    if a.policy == "qnet_mask":
+    prop, fuse, qnet, agent = PropagationNetwork(top_k=a.top_k, km=a.km), FusionNet(), None, None
+    if a.policy in ("qnet_mask",) + AGENT_POLICIES:
         from .qnet import QualityNet
         qnet = QualityNet()
     if a.synthetic_weights:
@@ -437,10 +536,13 @@ def main():
             qnet.load_state_dict(torch.load(a.qnet_weights, map_location="cpu"))
     if qnet is not None:
         qnet = qnet.cuda().eval()
+    if a.policy in AGENT_POLICIES:
+        from .agent import ActorCritic, PPOAgent
+        agent = (PPOAgent(state_dict=synth.recipe_state_dict(ActorCritic(), seed=5)) if a.synthetic_weights else PPOAgent(model_path=a.agent_weights))
     typed = a.policy in TYPED_POLICIES
     out = os.path.join("Experiments", a.db, "_".join([a.policy] + (sorted(a.annotation_types) if typed else [])) + ".csv")
     rows = run(a.root, a.imset, out, prop.eval(), fuse.eval(), a.policy, a.rounds, qnet=qnet, lanes=a.lanes, multi_object=a.multi_object,
-               share_frames=not a.no_share_frames, annotator=a.annotator if typed else None, annotation_types=a.annotation_types)
+               share_frames=not a.no_share_frames, annotator=a.annotator if typed or agent else None, annotation_types=a.annotation_types, agent=agent)
     if not dist.is_initialized() or dist.get_rank() == 0:
         print(f"{len(rows)} rounds -> {out}")
     if dist.is_initialized():

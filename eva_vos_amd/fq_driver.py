@@ -479,7 +479,7 @@ def new_frame_annotations(T: int) -> list:
     return [dict(annotations=[], click_labels=None, click_coords=None, bbox=None, sam_logits=None) for _ in range(T)]
 
 
-def typed_annotation_session(processor, scorer, T: int, rounds: int, gt, choose_action, next_frame, stats: dict = None):
+def typed_annotation_session(processor, scorer, T: int, rounds: int, gt, choose_action, next_frame, stats: dict = None, select=None):
     """The session loop of the mixed-annotation policies (interactions/mulitple_annotations.py:104-283; ``eva_vos``, :307-378, is the same
     loop with an agent behind ``choose_action``).  Round 1 annotates frame 0 with its mask at 80 s.  Round r > 1 annotates ``frames[-1]``:
     ``choose_action(frame, gen, frame_annots) -> (mask, cost, action, logits, clicks, labels, bbox)`` is the policy's annotation of it given the
@@ -487,7 +487,8 @@ def typed_annotation_session(processor, scorer, T: int, rounds: int, gt, choose_
     and interacts with the ground truth, every other action makes it type 2, hands the annotator's mask to ``scorer.set_annotation`` and
     keeps the prompts for a later annotation of the same frame.  The engine propagates (``processor.interact``), ``scorer`` (a
     metrics.TypedRoundScorer) evaluates, and ``next_frame(worst, types) -> frame or None`` picks the next one - frames REPEAT: a type-2 frame
-    stays selectable until it gets a mask.  Skip rules (:117-123): ``r >= T`` with every frame at quality 1, every frame annotated with a mask
+    stays selectable until it gets a mask; ``select(worst, types, gen, frames)``, when given, is called in its place: a selection that reads
+    the evaluated masks and the frames chosen so far (``eva_vos``'s QNet).  Skip rules (:117-123): ``r >= T`` with every frame at quality 1, every frame annotated with a mask
     (types: none but 1 left), or - after the first round - no frame left that is neither chosen nor without the object (not_avail_frames).
     ``gt``: [T,1,H,W] on the device.  Returns dict(frames, types, costs, actions): per scored round the annotated frame, its type (1 / 2), the
     seconds, the action; plus ``pending``: the frame chosen last, or None."""
@@ -525,7 +526,7 @@ def typed_annotation_session(processor, scorer, T: int, rounds: int, gt, choose_
         costs.append(cost)
         actions.append(action)
         fully = not (types != 1).any()
-        pending = next_frame(worst, types)
+        pending = next_frame(worst, types) if select is None else select(worst, types, gen, frames)
         if pending is not None:
             frames.append(int(pending))
     n = len(costs)

@@ -91,3 +91,32 @@ def qnet_frame_selection(qnet, frames: torch.Tensor, masks: torch.Tensor, intera
     imgs, m3 = to_224(frames, masks)
     feats = torch.cat([qnet.extract_features(imgs[i:i + batch], m3[i:i + batch]) for i in range(0, len(imgs), batch)])
     return select_farthest(feats, interacted)
+
+
+class QNetSelector:
+    """QNet frame selection of one video with the frames' half of the features cached: ``to_224`` of the clip and ``qnet.rgb_branch`` run once,
+    in batches of ``batch`` as ``qnet_frame_selection`` runs them; a round then costs the mask branch alone.  The cache holds only while
+    BatchNorm uses its frozen statistics, so a QNet in training mode is refused.  ``masks_to_input``: the route from the evaluated masks
+    (uint8 [T,H,W] on the device) to [T,3,224,224] fp32 - ``agent.masks_to_224`` (one HIP launch) unless another is given."""
+
+    @torch.no_grad()
+    def __init__(self, qnet, frames: torch.Tensor, batch: int = 64, masks_to_input=None):
+        if qnet.training:
+            raise ValueError("QNetSelector caches the frames' features: the QNet has to be in eval mode (frozen BatchNorm statistics), call qnet.eval()")
+        if masks_to_input is None:
+            from .agent import masks_to_224 as masks_to_input
+        self.qnet, self.batch, self.masks_to_input = qnet, batch, masks_to_input
+        imgs = F.interpolate(frames, size=(224, 224), mode="bicubic", antialias=True, align_corners=False)       # to_224's frames half
+        self.rgb = torch.cat([qnet.rgb_branch(imgs[i:i + batch]) for i in range(0, len(imgs), batch)])             # [T,512,1,1]
+
+    @torch.no_grad()
+    def features(self, gen: torch.Tensor) -> torch.Tensor:
+        """[T,1024]: what ``qnet.extract_features`` gives for the clip and these masks."""
+        if self.qnet.training:
+            raise ValueError("QNetSelector: the QNet was put into training mode after its frame features were cached")
+        m3 = self.masks_to_input(gen)
+        mask = torch.cat([self.qnet.mask_branch(m3[i:i + self.batch]) for i in range(0, len(m3), self.batch)])
+        return torch.cat((self.rgb, mask), 1).flatten(1)
+
+    def select(self, gen: torch.Tensor, interacted) -> int:
+        return select_farthest(self.features(gen), interacted)

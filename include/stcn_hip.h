@@ -632,6 +632,16 @@ int stcn_robot_bbox(void *stream, const uint8_t *mask_dev, int H, int W, int32_t
 #define STCN_ROBOT_BEST_INTS  (2 + 2 * STCN_ROBOT_MAX_CANDIDATES)
 int stcn_robot_best_mask(void *stream, const uint8_t *cand_dev, const uint8_t *target_dev, int M, int H, int W, int32_t *out_dev);
 
+/* ---- masks as network input (interactions/policies.py:12-18,44-45, mulitple_annotations.py:287-297) --------------------------------
+ * src uint8 [T,H,W] on the device (the masks a round evaluated, or a label map) -> out fp32 [n,channels,out_h,out_w]: resized with torch's
+ * `nearest` rule, per axis in fp32: source index = min((int)floorf(dst * ((float)in / out)), in - 1); the value of the byte as a float; all
+ * `channels` planes equal.  frames_dev: int32 [n] on the device, the frames to take, in that order, or NULL = the first n frames (n = T: all).
+ * A frame index outside [0,T) is not read: its planes are filled with NaN.  One launch on `stream`, no sync; only the sampled bytes are read.
+ * Null src / out, a size below 1, out_h * out_w above 2^24, frames_dev with n <= 0, n <= 0 or n > T without frames_dev, and n > 65535 return
+ * STCN_E_INVALID with a message before any device call. */
+int stcn_masks_resize_nearest(void *stream, const uint8_t *src, int T, int H, int W, const int32_t *frames_dev, int n, int out_h, int out_w,
+                              int channels, float *out);
+
 #ifdef __cplusplus
 }
 #endif
