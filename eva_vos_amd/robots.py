@@ -28,12 +28,28 @@ MAX_PIXELS = 1 << 24
 
 
 # ------------------------------------------------------------------------------------------------ host restatement
+def _frame_shape(shape):
+    """(H, W) of one mask given in any accepted shape, or None.  A 2-D mask is taken as it is - a [1,W] or [H,1] frame is a frame; a mask
+    with more dimensions loses its dimensions of extent one, and where that leaves fewer than two (the reference's [1,1,H,W] of a one-row
+    frame) the last two dimensions are the frame."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) == 2:
+        return shape
+    kept = tuple(v for v in shape if v != 1)
+    if len(kept) == 2:
+        return kept
+    if len(shape) > 2 and len(kept) < 2 and all(v == 1 for v in shape[:-2]):
+        return shape[-2:]
+    return None
+
+
 def _as_bool(mask) -> np.ndarray:
     if hasattr(mask, "detach"):
         mask = mask.detach().cpu().numpy()          # the download the reference's robot starts with (click_robot.py:15-16)
-    m = np.squeeze(np.asarray(mask)) != 0
-    assert m.ndim == 2, "one [H,W] mask"
-    return m
+    m = np.asarray(mask)
+    hw = _frame_shape(m.shape)
+    assert hw is not None, "one [H,W] mask"
+    return m.reshape(hw) != 0
 
 
 def _nearest_object_pixel(gt: np.ndarray, x: int, y: int):
@@ -156,11 +172,12 @@ def host_best_mask(candidates, target):
 
 # ------------------------------------------------------------------------------------------------ device robots
 def _mask_u8(mask):
-    """A torch mask on the device, any shape that squeezes to [H,W] -> uint8 [H,W] contiguous, non-zero = object (no sync)."""
+    """A torch mask on the device, [H,W] as it is or any shape that squeezes to [H,W] -> uint8 [H,W] contiguous, non-zero = object (no sync)."""
     import torch
-    m = mask.squeeze()
-    if m.dim() != 2 or not m.is_cuda:
+    hw = _frame_shape(mask.shape)
+    if hw is None or not mask.is_cuda:
         raise ValueError(f"a device robot takes one [H,W] mask on the GPU, got shape {tuple(mask.shape)} on {mask.device}")
+    m = mask.reshape(hw)
     if m.numel() == 0 or m.numel() > MAX_PIXELS:
         raise ValueError(f"a frame of {m.shape[0]} x {m.shape[1]} pixels: the robots take 1 .. 2^24")
     if m.dtype != torch.uint8:

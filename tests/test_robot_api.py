@@ -64,6 +64,47 @@ def test_an_empty_object_has_no_click_and_no_box():
     assert robots.HostBboxRobot().interact(z).tolist() == [[3.0, 2.0, 8.0, 4.0]]
 
 
+def test_a_frame_of_one_row_one_column_or_one_pixel_is_a_frame():
+    """A 2-D mask is taken as it is; only a mask with more dimensions loses those of extent one."""
+    row = np.zeros((1, 9), np.uint8)
+    row[0, 2:7] = 1
+    for gt, click, box in ((row, [4, 0], [1, 2, 0, 6, 0]), (row.T.copy(), [0, 4], [1, 0, 2, 0, 6])):
+        rec, comp = robots.host_click_record(np.zeros_like(gt), gt)
+        assert comp.shape == gt.shape and np.array_equal(comp, gt)
+        assert rec[:robots.MOVED + 1].tolist() == [1, click[0], click[1], 1, 0, 0, 0, 2, 0, 5, 0, 1, 0]
+        assert robots.host_click_record(None, gt, robots.MIDDLE)[0][:4].tolist() == [1, click[0], click[1], 1]
+        assert robots.host_bbox(gt).tolist() == box
+        clicks, labels = robots.HostClickRobot().interact(np.zeros_like(gt), gt)
+        assert clicks.tolist() == [click] and labels.tolist() == [1]
+        # the reference's [1,1,H,W] of the same frame, and a stack of candidates [M,1,H,W]
+        assert robots.host_click_record(np.zeros_like(gt)[None, None], gt[None, None])[0].tolist() == rec.tolist()
+        half = gt.copy()
+        half.reshape(-1)[2:4] = 0
+        iou, idx, counts = robots.host_best_mask(np.stack([half, gt, half])[:, None], gt)
+        assert (idx, iou) == (1, 1.0) and counts.tolist() == [[3, 5], [5, 5], [3, 5]]
+        assert robots.host_best_mask([half], gt[None])[2].tolist() == [[3, 5]]
+    one = np.ones((1, 1), np.uint8)
+    assert robots.host_click_record(0 * one, one)[0][:robots.MOVED + 1].tolist() == [1, 0, 0, 1, 0, 0, 0, 2, 0, 1, 0, 1, 0]
+    assert robots.host_click_record(one, 0 * one)[0][:robots.MOVED + 1].tolist() == [1, 0, 0, 0, 0, 0, 0, 1, 1, 0, 1, 0, 0]
+    assert robots.host_click_record(one, one)[0][:4].tolist() == [1, 0, 0, 1] and robots.host_click_record(one[None, None], one[None])[1].shape == (1, 1)
+    assert robots.host_bbox(one).tolist() == [1, 0, 0, 0, 0] and robots.host_bbox(0 * one).tolist() == [0] * 5
+    assert robots.host_best_mask([one, 0 * one], one)[:2] == (1.0, 0)
+    assert robots.scratch_bytes(1, 1) == 256 + 16 + 8              # the header, two histogram words rounded to 16 bytes, a parent and a size
+
+
+def test_every_shape_accepted_before_keeps_its_meaning():
+    m = np.arange(12).reshape(3, 4) % 3 == 0
+    for shape in ((3, 4), (1, 3, 4), (1, 1, 3, 4), (3, 4, 1), (1, 3, 1, 4), (3, 1, 4)):
+        assert np.array_equal(robots._as_bool(m.reshape(shape)), m)
+        assert robots._frame_shape(shape) == (3, 4)
+    for shape, hw in (((1, 4), (1, 4)), ((4, 1), (4, 1)), ((1, 1), (1, 1)), ((1, 1, 1, 4), (1, 4)), ((1, 1, 4, 1), (4, 1)), ((1, 1, 1, 1), (1, 1))):
+        assert robots._frame_shape(shape) == hw
+    for shape in ((4,), (), (2, 3, 4), (2, 1, 3, 4), (4, 1, 1)):
+        assert robots._frame_shape(shape) is None
+        with pytest.raises(AssertionError):
+            robots._as_bool(np.zeros(shape))
+
+
 @pytest.mark.parametrize("name", NEW)
 def test_the_new_symbols_are_declared_and_exported(name):
     assert name in _lib.PROTOTYPES and hasattr(_lib.lib(), name)
