@@ -452,11 +452,16 @@ int stcn_test_fusion(const stcn_model *m, void *stream, const float *img, const 
 // ---- J / F metrics: every argument is checked before any device call --------------------------------------------------------------------
 static int bound_radius(int H, int W) { return (int)std::ceil(0.008 * std::sqrt((double)H * H + (double)W * W)); }      // interactions/metrics.py:119-120
 
-// What all seven entry points check: k where the call has one (label maps), the shape - min_hw = 2 where a boundary map can be built, 1 for
-// the binary J-only call - and every pointer the call dereferences.
-static bool metric_args_ok(const char *who, bool has_k, int k, int T, int H, int W, int min_hw, std::initializer_list<const void *> ptrs) {
+// What all the entry points check: k where the call has one (label maps), the shape - min_hw = 2 where a boundary map can be built, 1 for
+// the binary J-only call - the disk radius where the call builds boundary maps (`disk`: disk_scan squares up to r + 1 in int, see
+// METRICS_MAX_RADIUS; the J-only forms have no disk and take any shape) and every pointer the call dereferences.
+static bool metric_args_ok(const char *who, bool has_k, int k, int T, int H, int W, int min_hw, bool disk, std::initializer_list<const void *> ptrs) {
     if (has_k && (k < 1 || k > STCN_MAX_OBJECTS)) { set_error("%s: k = %d outside 1..%d (STCN_MAX_OBJECTS)", who, k, STCN_MAX_OBJECTS); return false; }
     if (T < 1 || H < min_hw || W < min_hw) { set_error("%s: bad shape (T >= 1, H, W >= %d required; T=%d H=%d W=%d)", who, min_hw, T, H, W); return false; }
+    if (disk && bound_radius(H, W) > METRICS_MAX_RADIUS) {
+        set_error("%s: H=%d W=%d take a disk of radius %d, above the limit of %d (METRICS_MAX_RADIUS)", who, H, W, bound_radius(H, W), METRICS_MAX_RADIUS);
+        return false;
+    }
     for (const void *p : ptrs)
         if (!p) { set_error("%s: null pointer", who); return false; }
     return true;
@@ -464,14 +469,14 @@ static bool metric_args_ok(const char *who, bool has_k, int k, int T, int H, int
 
 int stcn_metrics_jf_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int T, int H, int W,
                            int32_t *counts_dev, uint8_t *scratch_dev) {
-    if (!metric_args_ok("stcn_metrics_jf_counts", false, 0, T, H, W, 2, {gt_dev, pred_dev, counts_dev, scratch_dev})) return STCN_E_INVALID;
+    if (!metric_args_ok("stcn_metrics_jf_counts", false, 0, T, H, W, 2, true, {gt_dev, pred_dev, counts_dev, scratch_dev})) return STCN_E_INVALID;
     jf_counts_launch(gt_dev, pred_dev, T, H, W, bound_radius(H, W), scratch_dev, counts_dev, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return STCN_OK;
 }
 
 int stcn_metrics_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int T, int H, int W, int32_t *counts_dev) {
-    if (!metric_args_ok("stcn_metrics_j_counts", false, 0, T, H, W, 1, {gt_dev, pred_dev, counts_dev})) return STCN_E_INVALID;
+    if (!metric_args_ok("stcn_metrics_j_counts", false, 0, T, H, W, 1, false, {gt_dev, pred_dev, counts_dev})) return STCN_E_INVALID;
     jf_counts_launch(gt_dev, pred_dev, T, H, W, -1, nullptr, counts_dev, (hipStream_t)stream);       // radius < 0: intersection / union only
     HIPCHK(hipGetLastError());
     return STCN_OK;
@@ -507,21 +512,21 @@ int stcn_frame_sq_distances(void *stream, const float *x_dev, int T, int64_t K, 
 }
 
 int stcn_metrics_objects_scratch(int k, int T, int H, int W, int64_t *bytes) {
-    if (!metric_args_ok("stcn_metrics_objects_scratch", true, k, T, H, W, 2, {bytes})) return STCN_E_INVALID;
+    if (!metric_args_ok("stcn_metrics_objects_scratch", true, k, T, H, W, 2, true, {bytes})) return STCN_E_INVALID;
     *bytes = (int64_t)label_scratch_bytes(k, T, H, W);
     return STCN_OK;
 }
 
 int stcn_metrics_objects_jf_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int k, int T, int H, int W, int32_t *counts_dev,
                                    void *scratch_dev) {
-    if (!metric_args_ok("stcn_metrics_objects_jf_counts", true, k, T, H, W, 2, {gt_dev, pred_dev, counts_dev, scratch_dev})) return STCN_E_INVALID;
+    if (!metric_args_ok("stcn_metrics_objects_jf_counts", true, k, T, H, W, 2, true, {gt_dev, pred_dev, counts_dev, scratch_dev})) return STCN_E_INVALID;
     label_counts_launch(gt_dev, pred_dev, k, T, H, W, bound_radius(H, W), scratch_dev, counts_dev, T, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return STCN_OK;
 }
 
 int stcn_metrics_objects_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int k, int T, int H, int W, int32_t *counts_dev) {
-    if (!metric_args_ok("stcn_metrics_objects_j_counts", true, k, T, H, W, 2, {gt_dev, pred_dev, counts_dev})) return STCN_E_INVALID;
+    if (!metric_args_ok("stcn_metrics_objects_j_counts", true, k, T, H, W, 2, false, {gt_dev, pred_dev, counts_dev})) return STCN_E_INVALID;
     label_counts_launch(gt_dev, pred_dev, k, T, H, W, -1, nullptr, counts_dev, T, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return STCN_OK;
@@ -534,7 +539,7 @@ static int metrics_round(const char *who, bool labels, void *stream, const uint8
                          uint8_t *gen_dev, void *scratch_dev, int32_t *counts_dev, double *object_quality_dev, double *quality_dev, int32_t *select_dev,
                          bool typed = false, const uint8_t *annot_dev = nullptr) {
     const void *unused = who;       // in the place of a pointer that this form of the call does not read
-    if (!metric_args_ok(who, labels, k, T, H, W, 2, {masks_dev, gt_dev, annotated_dev, flags_dev, gen_dev, counts_dev, labels ? object_quality_dev : unused,
+    if (!metric_args_ok(who, labels, k, T, H, W, 2, !j_only, {masks_dev, gt_dev, annotated_dev, flags_dev, gen_dev, counts_dev, labels ? object_quality_dev : unused,
                                                     quality_dev, select_dev, j_only ? unused : scratch_dev, typed ? annot_dev : unused}))
         return STCN_E_INVALID;
     if (lh < 0 || lw < 0 || lh + H > nh || lw + W > nw) { set_error("%s: the %d x %d crop at (%d, %d) leaves the %d x %d tensor", who, H, W, lh, lw, nh, nw); return STCN_E_INVALID; }
@@ -567,7 +572,7 @@ int stcn_metrics_trial(void *stream, const uint8_t *masks_dev, int nh, int nw, i
                        const int32_t *counts_dev, uint8_t *span_gen_dev, uint8_t *scratch_dev, int32_t *span_counts_dev, double *quality_dev) {
     const char *who = "stcn_metrics_trial";
     const void *unused = who;
-    if (!metric_args_ok(who, false, 0, T, H, W, 2, {masks_dev, gt_dev, annotated_dev, noobj_dev, counts_dev, span_gen_dev, span_counts_dev, quality_dev,
+    if (!metric_args_ok(who, false, 0, T, H, W, 2, !j_only, {masks_dev, gt_dev, annotated_dev, noobj_dev, counts_dev, span_gen_dev, span_counts_dev, quality_dev,
                                                     j_only ? unused : scratch_dev}))
         return STCN_E_INVALID;
     if (lh < 0 || lw < 0 || lh + H > nh || lw + W > nw) { set_error("%s: the %d x %d crop at (%d, %d) leaves the %d x %d tensor", who, H, W, lh, lw, nh, nw); return STCN_E_INVALID; }

@@ -240,6 +240,11 @@ struct MemReadScratch { float *cand_v; int32_t *cand_i; int32_t *cand_n; float *
 struct MemReadScratchSizes { size_t cand_v, cand_i, cand_n, gmax, tau; };
 MemReadScratchSizes memread_scratch_floats(int Q);
 constexpr long MAX_FRAME_PIXELS = 1L << 24;      // padded frame nh * nw an engine or a stage context is created for: the per-frame launches size their grids in 32 bits
+// largest disk radius r of the boundary measure (metrics.hip): disk_scan evaluates squares up to (r + 1)^2 in int, and 46340^2 =
+// 2 147 395 600 <= INT_MAX = 2 147 483 647 < 46341^2 = 2 147 488 281.  The entry points that build boundary maps refuse a larger one.
+constexpr int METRICS_MAX_RADIUS = 46339;
+static_assert((long)(METRICS_MAX_RADIUS + 1) * (METRICS_MAX_RADIUS + 1) <= 0x7fffffffL && (long)(METRICS_MAX_RADIUS + 2) * (METRICS_MAX_RADIUS + 2) > 0x7fffffffL,
+              "METRICS_MAX_RADIUS is the largest r with (r + 1)^2 <= INT_MAX");
 constexpr long MEMREAD_MAX_ROWS = 1L << 24;      // bank rows of one read: the read kernels build their key descriptor as (unsigned)N * 256 bytes, which wraps there
 constexpr int MEMREAD_MSQ_PAD = 64;     // readable floats behind the N values of msq: the read kernels fetch |mk|^2 in whole 64-row steps
 // dynamic LDS above 64 KB has to be opted into once per (device, kernel function)

@@ -497,6 +497,10 @@ int stcn_get_conv_regimes(stcn_engine *e, double *out /*[6]*/);
  *                      gt boundary px matched within the disk, pred boundary px matched within the disk
  *   scratch_dev      : uint8 [T*H*W]
  * The disk radius is ceil(0.008 * ||(H,W)||) as in the reference.  Enqueues on `stream`, no sync.
+ * RADIUS LIMIT of every call that builds boundary maps - this one, stcn_metrics_objects_scratch, stcn_metrics_objects_jf_counts, and
+ * stcn_metrics_round / _round_typed / _objects_round / _trial with j_only == 0: a shape whose radius exceeds 46339 (the disk scan squares
+ * up to radius + 1 in 32 bits; 2 x 5 792 375 is the first such thin frame) returns STCN_E_INVALID before any device call, the error text
+ * naming H, W, the radius and the limit.  The J-only forms have no disk and take any shape.
  * Replaces: get_j_and_f / f_measure / _seg2bmap (interactions/metrics.py:24-34,38-97,100-160) as called per
  * frame per round by eval_processor_metric (interactions/eval.py:50-79). */
 int stcn_metrics_jf_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int T, int H, int W,
@@ -512,6 +516,7 @@ int stcn_metrics_j_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pr
  *   gt_dev        : uint8 [T,H,W] ground truth, non-zero = object;  annotated_dev / noobj_dev : uint8 [T] flags
  *   gen_dev       : uint8 [T,H,W] OUT - the evaluated masks (engine mask, GT on annotated frames): the state util/fq_dataset.py:64-84 saves
  *   scratch_dev   : uint8 [T*H*W] (unused when j_only);  counts_dev : int32 [T,6] OUT as stcn_metrics_jf_counts
+ *   j_only == 0   : the radius limit of stcn_metrics_jf_counts applies
  *   quality_dev   : double [T] OUT - per-frame J (j_only) or J&F, no_object for flagged frames; fp64 with the host path's operations in the
  *                   host path's order, i.e. bit-identical to it;  select_dev : int32 [1] OUT - first index of the minimum (numpy.argmin)
  * Only select (4 bytes) has to cross PCIe per round; the quality rows of a session can be fetched together at its end.
@@ -533,7 +538,8 @@ int stcn_metrics_round(void *stream, const uint8_t *masks_dev, int nh, int nw, i
  *   quality_dev    : double [T] OUT - per frame the value stcn_metrics_round would write after a real round with this annotation, to the bit:
  *                    from the span's counts inside [t0, t1), from counts_dev outside, no_object for flagged frames
  * Nothing else is written: no gen, no counts, no selection - the caller's round state is what it was.  Null pointers, t0 > t1, a span or a
- * candidate outside [0, T) return STCN_E_INVALID before any device call. */
+ * candidate outside [0, T) and, with j_only == 0, a radius above the limit of stcn_metrics_jf_counts return STCN_E_INVALID before any
+ * device call. */
 int stcn_metrics_trial(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev, const uint8_t *annotated_dev,
                        const uint8_t *noobj_dev, int candidate, int T, int H, int W, int t0, int t1, int j_only, double no_object,
                        const int32_t *counts_dev, uint8_t *span_gen_dev, uint8_t *scratch_dev, int32_t *span_counts_dev, double *quality_dev);
@@ -544,11 +550,12 @@ int stcn_metrics_trial(void *stream, const uint8_t *masks_dev, int nh, int nw, i
  * All objects are served by ONE pass over the pixels: the number of launches does not depend on k.
  *
  * Boundary scratch of the calls below for k objects and T frames of H x W, in BYTES (the one statement of its size: a per-pixel set of
- * objects per map - bytes for k <= 8, 32-bit words above).  Works without a GPU. */
+ * objects per map - bytes for k <= 8, 32-bit words above).  Works without a GPU.  Refuses a shape above the radius limit of
+ * stcn_metrics_jf_counts, as the calls that take the scratch do. */
 int stcn_metrics_objects_scratch(int k, int T, int H, int W, int64_t *bytes);
 /* Per object the counts of stcn_metrics_jf_counts for the binary masks (gt == o), (pred == o), integer-exact:
  *   gt_dev, pred_dev : uint8 [T,H,W] label maps;  counts_dev : int32 [k,T,6] OUT;  scratch_dev : stcn_metrics_objects_scratch bytes.
- * Enqueues on `stream`, no sync. */
+ * Enqueues on `stream`, no sync.  The radius limit of stcn_metrics_jf_counts applies. */
 int stcn_metrics_objects_jf_counts(void *stream, const uint8_t *gt_dev, const uint8_t *pred_dev, int k, int T, int H, int W,
                                    int32_t *counts_dev, void *scratch_dev);
 /* The region measure alone, as stcn_metrics_j_counts: columns 0 and 1 of counts_dev [k,T,6] filled, the others zero; no scratch. */
@@ -564,7 +571,8 @@ int stcn_metrics_objects_j_counts(void *stream, const uint8_t *gt_dev, const uin
  *   quality_dev        : double [T] OUT - the mean of object_quality over the objects present in the frame: added in ascending o, then divided
  *                        by their number (correctly rounded fp64, bit-identical to eva_vos_amd.metrics.label_round_quality); no_object for a
  *                        frame without any object;  select_dev : int32 [1] OUT - first index of the minimum of quality_dev (numpy.argmin)
- * [t0, t1) as in stcn_metrics_round: only those frames are composed and counted, quality / select cover all T frames. */
+ * [t0, t1) as in stcn_metrics_round: only those frames are composed and counted, quality / select cover all T frames; with j_only == 0 the
+ * radius limit of stcn_metrics_jf_counts applies. */
 int stcn_metrics_objects_round(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev,
                                const uint8_t *annotated_dev, const uint8_t *present_dev, int k, int T, int H, int W, int t0, int t1, int j_only,
                                double no_object, uint8_t *gen_dev, void *scratch_dev, int32_t *counts_dev, double *object_quality_dev,
@@ -576,7 +584,7 @@ int stcn_metrics_objects_round(void *stream, const uint8_t *masks_dev, int nh, i
  *   type_dev  : uint8 [T] - 0 = the engine's mask, 1 = ground truth, 2 = annotator mask (any other non-zero value counts as 1)
  *   annot_dev : uint8 [T,H,W], non-zero = object - the current annotator mask of every type-2 frame; other frames are not read
  * Binary masks only (the reference's typed policies are one-object).  Counts, quality, arg-min and the [t0, t1) contract are those of
- * stcn_metrics_round; without a type-2 frame the outputs are its outputs, bit for bit. */
+ * stcn_metrics_round, and so is the radius limit when j_only == 0; without a type-2 frame the outputs are its outputs, bit for bit. */
 int stcn_metrics_round_typed(void *stream, const uint8_t *masks_dev, int nh, int nw, int lh, int lw, const uint8_t *gt_dev, const uint8_t *type_dev,
                              const uint8_t *annot_dev, const uint8_t *noobj_dev, int T, int H, int W, int t0, int t1, int j_only, double no_object,
                              uint8_t *gen_dev, uint8_t *scratch_dev, int32_t *counts_dev, double *quality_dev, int32_t *select_dev);
