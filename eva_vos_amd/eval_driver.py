@@ -2,8 +2,9 @@
 
 Own counterpart of the reference driver ``eval_annotation_method.py:118-190`` for the policies whose annotations are
 ground-truth masks - ``oracle_mask``, ``rand_mask``, ``qnet_mask``, ``upper_bound_mask``, ``l2_mask`` (``interactions/mask.py:10-39,
-42-71,74-103,196-227,159-193``) - with their helpers ``initialize`` / ``not_avail_frames`` / ``eval_processor_metric``
-(``interactions/eval.py:27-117``) and the frame selectors of ``interactions/policies.py``.  The click / bbox policies
+42-71,74-103,196-227,159-193``) - and the frame selectors of ``interactions/policies.py``; every ``run_*`` below builds a scorer and a
+``SessionPolicy`` record for the one session loop of ``eva_vos_amd/sessions.py``, POLICY_TABLE says what ``run`` and the command line know
+of each policy (its runner, what it needs, its modes, its extra columns), the dataset and lane side is ``fq_driver``'s.  The click / bbox policies
 additionally need SAM (``segment_anything``), which north_star leaves on stock PyTorch-ROCm and which is not installed offline; the
 mixed-annotation policies (``run_typed_policy``) and ``eva_vos`` itself (``run_eva_vos``: the QNet picks the frame, the actor-critic agent
 the annotation type) therefore run over any predictor with the SAM controller's signature, the ``ComponentPredictor`` stand-in included.
@@ -34,27 +35,23 @@ import copy
 import csv
 import os
 import random
+import threading
 import time
+from collections import namedtuple
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import Callable
 
 import numpy as np
 import torch
 
-from . import metrics, shard
+from . import metrics
 from .frame_select import farthest_frame
-from .fq_driver import NO_OBJECT, ClipDataset, LaneCores, annotation_session, frame_quality, lane_engine_options, run_lanes, typed_annotation_session
+from .fq_driver import ClipDataset, add_stats, gather_sorted, lane_cores, load_networks, rank_samples, report_and_leave, run_lanes
+from .sessions import MASK_SECONDS, NO_OBJECT, SKIP_SECONDS, SessionPolicy, annotation_session, frame_quality, session_result
 
-POLICIES = ("oracle_mask", "rand_mask", "qnet_mask", "upper_bound_mask", "l2_mask")
-# QNet takes one binary mask; the upper bound builds on the one-object scorer; the l2 selector needs no mask at all
-MULTI_OBJECT_POLICIES = ("oracle_mask", "rand_mask", "l2_mask")
-# the mixed-annotation policies (interactions/mulitple_annotations.py:104-283): run_typed_policy, with an annotator; one-object sessions
-TYPED_POLICIES = ("rand_type", "rand_rand", "oracle_oracle")
-# eva_vos (interactions/mulitple_annotations.py:286-378): run_eva_vos, with an annotator, the QNet and the agent; one-object sessions
-AGENT_POLICIES = ("eva_vos",)
 ANNOTATORS = ("component",)                                   # built in; a real SAM controller is passed through run(..., annotator=...)
 MAX_OBJECTS = 32                                              # STCN_MAX_OBJECTS
-MASK_SECONDS, SKIP_SECONDS = 80, 3            # annotation cost model of interactions/mask.py:33-36
-
-
 KEY_CACHE_FRAMES = 106                                       # the engine's key cache: a clip of at most this many frames never recycles a slot
 
 
@@ -132,26 +129,24 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
     _check_l2_clip(policy, T, f"clip {sample.get('name', '?')}")
     dev = processor.prob.device
     rng = rng or random
+    stats = {} if stats is None else stats
     # the evaluation of a round stays on the device (metrics.RoundScorer): one int per round crosses PCIe for the oracle policy, the
     # per-frame quality rows of the whole session are fetched once at the end
-    scorer_args = dict(max_rounds=max(rounds, 1), no_object=NO_OBJECT)
+    scorer_args = dict(metric="j" if metric == "j" else "j_and_f", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
     if multi_object:
         k = int(sample["num_objects"])
-        scorer = metrics.RoundScorer(sample["gt"][0, :, 0].to(dev), "j" if metric == "j" else "j_and_f", num_objects=k, **scorer_args)
+        scorer = metrics.RoundScorer(sample["gt"][0, :, 0].to(dev), num_objects=k, **scorer_args)
         channels = torch.arange(k + 1, device=dev, dtype=torch.uint8)[:, None, None, None]
-
-        def annotate(f):
-            processor.interact((scorer.gt[f][None, None] == channels).float(), f, scribble=True, download=False)      # [k+1,1,H,W]
+        mask_of, interact_kw = (lambda f: (scorer.gt[f][None, None] == channels).float()), dict(scribble=True)      # [k+1,1,H,W]
     else:
         gt = sample["gt"][0].to(dev)                               # [T,1,H,W]
         gt_thw = gt[:, 0]
         images = sample["rgb"][0].to(dev) if policy == "qnet_mask" else None
-        scorer = metrics.RoundScorer(gt_thw, "j" if metric == "j" else "j_and_f", **scorer_args)
+        scorer = metrics.RoundScorer(gt_thw, **scorer_args)
+        mask_of, interact_kw = (lambda f: gt[f][None]), {}
+    in_place = policy == "upper_bound_mask" and T <= KEY_CACHE_FRAMES
 
-        def annotate(f):
-            processor.interact(gt[f][None], f, download=False)
-
-    def choose(worst, gen, frames):
+    def choose(worst, types, gen, frames):
         if policy == "oracle_mask":
             return worst
         if policy == "rand_mask":
@@ -165,9 +160,7 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
             return _upper_bound_frame_in_place(processor, scorer, gt, frames, stats)
         return _upper_bound_frame(processor, gt, gt_thw, frames, metric, stats)
 
-    stats = {} if stats is None else stats
-    seen = stats.get("propagated_frames", 0)
-    in_place = policy == "upper_bound_mask" and T <= KEY_CACHE_FRAMES
+    session = SessionPolicy(mask_of, choose, keep_gen=policy == "qnet_mask", interact_kw=interact_kw)
     if policy == "upper_bound_mask":
         stats.setdefault("trial_interactions", 0), stats.setdefault("engine_clones", 0)
     depth = processor.undo_state()["depth"] if in_place else 0
@@ -175,21 +168,16 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
         processor.set_undo_depth(max(depth, 1))
     passes = processor.frame_distance_passes if policy == "l2_mask" else 0
     try:
-        frames, gens = annotation_session(processor, scorer, T, rounds, annotate, choose, keep_gen=policy == "qnet_mask", stats=stats)
+        ses = annotation_session(processor, scorer, T, rounds, session, stats)
     finally:
         if in_place:
             processor.set_undo_depth(depth)                        # the core goes back to its lane as it came
     if policy == "l2_mask":
         stats["frame_distance_passes"] = stats.get("frame_distance_passes", 0) + processor.frame_distance_passes - passes
-    empty, scored = scorer.empty_host, len(gens)
-    times = [MASK_SECONDS] + [SKIP_SECONDS if empty[f] else MASK_SECONDS for f in frames[1:]]
-    q = scorer.qualities()
-    per_round = [q[i].copy() for i in range(scored)]
-    mus = [float(np.mean(row[~empty])) if (~empty).any() else float("nan") for row in per_round]
-    res = dict(mu_metrics=mus, annotation_times=times[:-1], frames=frames, round_metrics=per_round, propagated_frames=stats.get("propagated_frames", 0) - seen)
+    res = dict(session_result(scorer, ses), frames=ses["chosen"])
     if multi_object:
         oq = scorer.object_qualities()
-        res.update(object_metrics=[oq[i].copy() for i in range(scored)], present=scorer.present_host)
+        res.update(object_metrics=[oq[i].copy() for i in range(len(ses["costs"]))], present=scorer.present_host)
     return res
 
 
@@ -213,6 +201,18 @@ def oracle_action(annotator, annotation_types, gt_mask, mivos_mask, im, frame_an
     return best + (data,)
 
 
+def _one_object_session(policy: str, processor, sample, rounds: int, metric: str, scorer):
+    """What the one-object sessions with other annotations than masks start from: (T, gt [T,1,H,W] and the clip [T,3,H,W] on the engine's
+    device, the scorer - a metrics.TypedRoundScorer unless the caller brought one).  A per-video sample is refused."""
+    if "object_ids" in sample:                                      # ClipDataset(..., per_video=True)
+        raise ValueError(f"{policy} is a one-object policy: multi-object sessions support {' and '.join(MULTI_OBJECT_POLICIES)}")
+    dev = processor.prob.device
+    gt = sample["gt"][0].to(dev)
+    if scorer is None:
+        scorer = metrics.TypedRoundScorer(gt[:, 0], "j" if metric == "j" else "j_and_f", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
+    return sample["num_frames"], gt, sample["rgb"][0].to(dev), scorer
+
+
 def run_typed_policy(policy: str, processor, sample, rounds: int, annotator, annotation_types, metric: str = "j_and_f", rng=None,
                      stats: dict = None, scorer=None, choose_action=None):
     """One sample through ``rounds`` rounds of a mixed-annotation policy (``rand_type``, ``rand_rand``, ``oracle_oracle``:
@@ -233,15 +233,8 @@ def run_typed_policy(policy: str, processor, sample, rounds: int, annotator, ann
         raise ValueError(f"rand_type takes one annotation type, got {types_}")
     if policy != "rand_type" and len(types_) < 2:
         raise ValueError(f"{policy} requires more than one annotation type, got {types_}")
-    if "object_ids" in sample:                                      # a per-video sample (ClipDataset(..., per_video=True))
-        raise ValueError(f"{policy} is a one-object policy: multi-object sessions support {' and '.join(MULTI_OBJECT_POLICIES)}")
-    T = sample["num_frames"]
-    dev = processor.prob.device
+    T, gt, images, scorer = _one_object_session(policy, processor, sample, rounds, metric, scorer)
     rng = rng or random
-    gt = sample["gt"][0].to(dev)                                   # [T,1,H,W]
-    images = sample["rgb"][0].to(dev)
-    if scorer is None:
-        scorer = metrics.TypedRoundScorer(gt[:, 0], "j" if metric == "j" else "j_and_f", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
     empty = scorer.empty_host
     action_data = []
 
@@ -255,21 +248,16 @@ def run_typed_policy(policy: str, processor, sample, rounds: int, annotator, ann
         mask, cost, _, logits, clicks, labels, bbox = annotator.annotate(action, g, images[frame], mivos, frame_annots, empty=bool(empty[frame]))
         return mask, cost, action, logits, clicks, labels, bbox
 
-    def next_frame(worst, types):
+    def choose_frame(worst, types, gen, frames):
         if policy == "oracle_oracle":
             return worst
         left = np.where(types != 1)[0]
         return int(rng.choice(left.tolist())) if len(left) else None
 
-    stats = {} if stats is None else stats
-    seen = stats.get("propagated_frames", 0)
-    ses = typed_annotation_session(processor, scorer, T, rounds, gt, choose_action or policy_action, next_frame, stats=stats)
-    q = scorer.qualities()
-    per_round = [q[i].copy() for i in range(len(ses["costs"]))]
-    mus = [float(np.mean(row[~empty])) if (~empty).any() else float("nan") for row in per_round]
-    return dict(mu_metrics=mus, annotation_times=ses["costs"], annotations_actions=ses["actions"], round_metrics=per_round,
-                annotated_frames=ses["frames"], frames=ses["frames"], types=ses["types"], action_data=action_data,
-                propagated_frames=stats.get("propagated_frames", 0) - seen)
+    session = SessionPolicy(lambda f: gt[f][None], choose_frame, action=choose_action or policy_action, stop_at_T=False)
+    ses = annotation_session(processor, scorer, T, rounds, session, {} if stats is None else stats)
+    return dict(session_result(scorer, ses), annotations_actions=ses["actions"], annotated_frames=ses["frames"], frames=ses["frames"], types=ses["types"],
+                action_data=action_data)
 
 
 def run_eva_vos(processor, sample, rounds: int, annotator, qnet, agent, metric: str = "j_and_f", rng=None, stats: dict = None, scorer=None,
@@ -286,14 +274,7 @@ def run_eva_vos(processor, sample, rounds: int, annotator, qnet, agent, metric: 
     ``annotations_actions``, ``round_metrics``, ``annotated_frames`` - plus ``frames``, ``types`` and ``propagated_frames``."""
     from .agent import AVAIL_ACTIONS, masks_to_224
     from .annotate import ANNOTATION_COSTS
-    if "object_ids" in sample:                                      # a per-video sample (ClipDataset(..., per_video=True))
-        raise ValueError(f"eva_vos is a one-object policy: multi-object sessions support {' and '.join(MULTI_OBJECT_POLICIES)}")
-    T = sample["num_frames"]
-    dev = processor.prob.device
-    gt = sample["gt"][0].to(dev)                                   # [T,1,H,W]
-    images = sample["rgb"][0].to(dev)
-    if scorer is None:
-        scorer = metrics.TypedRoundScorer(gt[:, 0], "j" if metric == "j" else "j_and_f", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
+    T, gt, images, scorer = _one_object_session("eva_vos", processor, sample, rounds, metric, scorer)
     if selector is None:
         from .qnet import QNetSelector
         selector = QNetSelector(qnet, images)
@@ -321,14 +302,10 @@ def run_eva_vos(processor, sample, rounds: int, annotator, qnet, agent, metric: 
         left = np.where(types != 1)[0]
         return selector.select(gen, left.tolist()) if len(left) else None
 
-    stats = {} if stats is None else stats
-    seen = stats.get("propagated_frames", 0)
-    ses = typed_annotation_session(processor, scorer, T, rounds, gt, choose_action, None, stats=stats, select=select)
-    q = scorer.qualities()
-    per_round = [q[i].copy() for i in range(len(ses["costs"]))]
-    mus = [float(np.mean(row[~empty])) if (~empty).any() else float("nan") for row in per_round]
-    return dict(mu_metrics=mus, annotation_times=ses["costs"], rl_values=rl_values, annotations_actions=ses["actions"], round_metrics=per_round,
-                annotated_frames=ses["frames"], frames=ses["frames"], types=ses["types"], propagated_frames=stats.get("propagated_frames", 0) - seen)
+    session = SessionPolicy(lambda f: gt[f][None], select, action=choose_action, stop_at_T=False)
+    ses = annotation_session(processor, scorer, T, rounds, session, {} if stats is None else stats)
+    return dict(session_result(scorer, ses), rl_values=rl_values, annotations_actions=ses["actions"], annotated_frames=ses["frames"], frames=ses["frames"],
+                types=ses["types"])
 
 
 def make_annotator(name: str):
@@ -337,6 +314,92 @@ def make_annotator(name: str):
     if name != "component":
         raise ValueError(f"unknown annotator {name!r}: built in are {', '.join(ANNOTATORS)}; pass a PromptAnnotator over a SAM controller to run()")
     return PromptAnnotator(ComponentPredictor())
+
+
+# ------------------------------------------------------------------------------------------------ the policy table
+# a row column beyond the common ones: its CSV name, fill(res, r, action_names) - the float a row keeps for round r of a session's result -
+# and cell(value, action_names) - what the CSV shows for it
+Column = namedtuple("Column", "name fill cell")
+ACTIONS = Column("annotation_actions", lambda res, r, names: names.index(res["annotations_actions"][r]), lambda v, names: names[int(v)])
+VALUES = Column("rl_values", lambda res, r, names: res["rl_values"][r], lambda v, names: float(v))
+# what run() may have to be given, as the error message names it
+ARGUMENTS = {"qnet": "a QualityNet in eval mode", "agent": "an agent.PPOAgent", "annotator": "'component' or a factory of PromptAnnotator objects",
+             "annotation_types": "'click', 'bbox', 'mask' or '<N>clicks': one type for rand_type, several for the others"}
+
+
+@dataclass(frozen=True)
+class PolicySpec:
+    """All that run() and main() know of a policy.  ``runner(job, proc, sample, i, session_stats)``: sample i through its session (``job``: the
+    arguments of run() and ``lane``, what the lane thread keeps between its sessions: its annotator, eva_vos's selector); ``needs``: the keys of ARGUMENTS the policy cannot run without; ``multi_object``:
+    it has a multi-object mode; ``tail``: its extra columns in CSV order, kept at the END of a row, column j at ``row[-1 - j]``;
+    ``action_names(annotation_types)``: the names an ACTIONS column indexes; ``seconds``: how the CSV prints ``annotation_time`` - the mask
+    policies cost whole seconds, click costs are fractions of one."""
+    runner: Callable
+    needs: tuple = ()
+    multi_object: bool = False
+    tail: tuple = ()
+    action_names: Callable = None
+    seconds: type = int
+
+
+def _run_mask(job, proc, sample, i, session):
+    return run_policy(job.policy, proc, sample, job.rounds, job.metric, job.qnet, random.Random(job.seed * 100003 + i), multi_object=job.multi_object,
+                      stats=session)
+
+
+def _run_typed(job, proc, sample, i, session):
+    return run_typed_policy(job.policy, proc, sample, job.rounds, job.lane.annotator, job.annotation_types, job.metric,
+                            random.Random(job.seed * 100003 + i), stats=session)
+
+
+def _run_agent(job, proc, sample, i, session):
+    lane, selector = job.lane, None
+    if job.share_frames:                                            # the sessions of a video's objects: one clip, one pass of the QNet's frame branch
+        if getattr(lane, "video", None) != sample["video"]:
+            from .qnet import QNetSelector
+            lane.video, lane.selector = sample["video"], QNetSelector(job.qnet, sample["rgb"][0])
+        selector = lane.selector
+    return run_eva_vos(proc, sample, job.rounds, lane.annotator, job.qnet, job.agent, job.metric, torch.Generator().manual_seed(job.seed * 100003 + i),
+                       stats=session, selector=selector)
+
+
+def _typed_action_names(annotation_types):
+    from .annotate import check_annotation_types
+    return sorted(set(check_annotation_types(annotation_types or ())) | {"mask"})
+
+
+# the mixed-annotation policies (interactions/mulitple_annotations.py:104-283): run_typed_policy, with an annotator; one-object sessions
+_TYPED = PolicySpec(_run_typed, needs=("annotator", "annotation_types"), tail=(ACTIONS,), action_names=_typed_action_names, seconds=float)
+POLICY_TABLE = {
+    # QNet takes one binary mask; the upper bound builds on the one-object scorer; the l2 selector needs no mask at all
+    "oracle_mask": PolicySpec(_run_mask, multi_object=True),
+    "rand_mask": PolicySpec(_run_mask, multi_object=True),
+    "qnet_mask": PolicySpec(_run_mask, needs=("qnet",)),
+    "upper_bound_mask": PolicySpec(_run_mask),
+    "l2_mask": PolicySpec(_run_mask, multi_object=True),
+    "rand_type": _TYPED,
+    "rand_rand": _TYPED,
+    "oracle_oracle": _TYPED,
+    # eva_vos (interactions/mulitple_annotations.py:286-378): run_eva_vos, with an annotator, the QNet and the agent; one-object sessions
+    "eva_vos": PolicySpec(_run_agent, needs=("qnet", "agent", "annotator"), tail=(VALUES, ACTIONS), seconds=float,
+                          action_names=lambda annotation_types: sorted({"3clicks", "mask", "no_object"})),
+}
+POLICIES, TYPED_POLICIES, AGENT_POLICIES = (tuple(n for n, p in POLICY_TABLE.items() if p.runner is runner) for runner in (_run_mask, _run_typed, _run_agent))
+MULTI_OBJECT_POLICIES = tuple(n for n, p in POLICY_TABLE.items() if p.multi_object)
+
+
+def _session_rows(res: dict, i: int, sample, multi_object: bool):
+    """(sample id, round, mu_metric, seconds, annotated frame, per-frame values) of every row a session's result gives: one per round, and in
+    multi-object mode one per object and round, with the object's id in the per-object enumeration."""
+    if not multi_object:
+        for r, (mu, sec, q) in enumerate(zip(res["mu_metrics"], res["annotation_times"], res["round_metrics"])):
+            yield i, r, mu, sec, res["frames"][r], q
+        return
+    for o, sid in enumerate(sample["object_ids"]):
+        here = res["present"][o]
+        for r, oq in enumerate(res["object_metrics"]):
+            f = res["frames"][r]
+            yield sid, r, float(np.mean(oq[o][here])) if here.any() else float("nan"), MASK_SECONDS if here[f] else SKIP_SECONDS, f, oq[o]
 
 
 def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "oracle_mask", rounds: int = 60,
@@ -363,30 +426,15 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     enumeration, one per (video, object, round), so the outputs of the two modes join on (sample id, round): mu_metric = the mean of that
     object's quality over the frames where it is present, annotation_time = 80 s if the object is present in the annotated frame, else
     3 s, the annotated frame is the session's, the per-frame values are that object's."""
-    import torch.distributed as dist
-
     from mivos.inference_core import InferenceCore
-    rank = dist.get_rank() if dist.is_initialized() else 0
-    world = dist.get_world_size() if dist.is_initialized() else 1
-    if multi_object and policy not in MULTI_OBJECT_POLICIES:
+    spec = POLICY_TABLE[policy]
+    if multi_object and not spec.multi_object:
         raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
-    typed = policy in TYPED_POLICIES
-    agent_policy = policy in AGENT_POLICIES
-    if agent_policy:
-        for name, given in (("qnet", qnet), ("agent", agent), ("annotator", annotator)):
-            if given is None:
-                raise ValueError(f"{policy} needs {name}=...: a QualityNet in eval mode, an agent.PPOAgent and an annotator ('component' or a factory "
-                                 "of PromptAnnotator objects)")
-        action_names = sorted({"3clicks", "mask", "no_object"})
-        lane_selectors = __import__("threading").local()
-    if typed:
-        from .annotate import check_annotation_types
-        action_names = sorted(set(check_annotation_types(annotation_types or ())) | {"mask"})
-        if annotator is None:
-            raise ValueError(f"{policy} needs an annotator: 'component' or a factory of PromptAnnotator objects")
-    if typed or agent_policy:
-        make = (lambda: make_annotator(annotator)) if isinstance(annotator, str) else annotator
-        lane_annotators = __import__("threading").local()
+    given = dict(qnet=qnet, agent=agent, annotator=annotator, annotation_types=annotation_types)
+    for name in spec.needs:
+        if given[name] is None:
+            raise ValueError(f"{policy} needs {name}=...: {ARGUMENTS[name]}")
+    action_names = spec.action_names(annotation_types) if spec.action_names else None
     ds = ClipDataset(root, imset, per_video=multi_object)
     for v, k, _ in ds.samples if multi_object else ():
         if k > MAX_OBJECTS:
@@ -394,91 +442,49 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     t_max = max(s[2] for s in ds.samples)
     _check_l2_clip(policy, t_max, "the longest clip")
     share_frames = share_frames and not multi_object
-    if share_frames:
-        mine = sorted(shard.lpt_assign_grouped([s[2] for s in ds.samples], [s[0] for s in ds.samples], world)[rank])      # the objects of a video share an engine
-    else:
-        mine = sorted(shard.lpt_assign([s[2] * (s[1] if multi_object else 1) for s in ds.samples], world)[rank])      # multi-object: frames x objects
-    cores = LaneCores(lambda sample: InferenceCore(prop_net, fuse_net, sample["rgb"], sample["num_objects"] if multi_object else 1,
-                                                   engine_options=lane_engine_options(lanes)), share_frames)
-    width = 6 + t_max + (1 if typed else 2 if agent_policy else 0)
-    stats_lock = __import__("threading").Lock()
+    rank, mine = rank_samples(ds, share_frames, multi_object)
+    cores = lane_cores(InferenceCore, prop_net, fuse_net, lanes, share_frames, multi_object)
+    width = 6 + t_max + len(spec.tail)
+    job = SimpleNamespace(policy=policy, rounds=rounds, metric=metric, qnet=qnet, agent=agent, annotation_types=annotation_types, seed=seed,
+                          multi_object=multi_object, share_frames=share_frames, lane=threading.local())
 
     def work(i, sample):
-        rows = []
         t_c = time.perf_counter()
         proc = cores.core_for(sample)
         t_s = time.perf_counter()
         session = {}
-        if (typed or agent_policy) and not hasattr(lane_annotators, "a"):
-            lane_annotators.a = make()
-        if agent_policy:
-            selector = None
-            if share_frames:                                        # the sessions of a video's objects: one clip, one pass of the QNet's frame branch
-                if getattr(lane_selectors, "video", None) != sample["video"]:
-                    from .qnet import QNetSelector
-                    lane_selectors.video, lane_selectors.s = sample["video"], QNetSelector(qnet, sample["rgb"][0])
-                selector = lane_selectors.s
-            res = run_eva_vos(proc, sample, rounds, lane_annotators.a, qnet, agent, metric, torch.Generator().manual_seed(seed * 100003 + i),
-                              stats=session, selector=selector)
-        elif typed:
-            res = run_typed_policy(policy, proc, sample, rounds, lane_annotators.a, annotation_types, metric, random.Random(seed * 100003 + i), stats=session)
-        else:
-            res = run_policy(policy, proc, sample, rounds, metric, qnet, random.Random(seed * 100003 + i), multi_object=multi_object, stats=session)
+        if "annotator" in spec.needs and not hasattr(job.lane, "annotator"):         # one per lane thread
+            job.lane.annotator = make_annotator(annotator) if isinstance(annotator, str) else annotator()
+        res = spec.runner(job, proc, sample, i, session)
         cores.done(proc)
-        if stats is not None:
-            with stats_lock:
-                stats["create_s"] = stats.get("create_s", 0.0) + t_s - t_c
-                stats["session_s"] = stats.get("session_s", 0.0) + time.perf_counter() - t_s
-                stats["propagated_frames"] = stats.get("propagated_frames", 0) + res["propagated_frames"]
-                stats["interactions"] = stats.get("interactions", 0) + len(res["mu_metrics"])
-                for n in ("trial_interactions", "engine_clones", "frame_distance_passes"):
-                    if n in session:
-                        stats[n] = stats.get(n, 0) + session[n]
-        if multi_object:
-            for o, sid in enumerate(sample["object_ids"]):
-                here = res["present"][o]
-                for r, oq in enumerate(res["object_metrics"]):
-                    row = np.full(width, np.nan, np.float32)
-                    f = res["frames"][r]
-                    row[:6] = (sid, r, float(np.mean(oq[o][here])) if here.any() else float("nan"), MASK_SECONDS if here[f] else SKIP_SECONDS, f, oq.shape[1])
-                    row[6:6 + oq.shape[1]] = oq[o]
-                    rows.append(row)
-            return rows
-        for r, (mu, sec, q) in enumerate(zip(res["mu_metrics"], res["annotation_times"], res["round_metrics"])):
+        add_stats(stats, dict({n: session[n] for n in ("trial_interactions", "engine_clones", "frame_distance_passes") if n in session},
+                              create_s=t_s - t_c, session_s=time.perf_counter() - t_s, propagated_frames=res["propagated_frames"],
+                              interactions=len(res["mu_metrics"])))
+        rows = []
+        for sid, r, mu, sec, f, q in _session_rows(res, i, sample, multi_object):
             row = np.full(width, np.nan, np.float32)
-            row[:6] = (i, r, mu, sec, res["frames"][r], len(q))
+            row[:6] = (sid, r, mu, sec, f, len(q))
             row[6:6 + len(q)] = q
-            if typed:
-                row[-1] = action_names.index(res["annotations_actions"][r])
-            if agent_policy:
-                row[-2:] = (action_names.index(res["annotations_actions"][r]), res["rl_values"][r])
+            for j, col in enumerate(spec.tail):
+                row[-1 - j] = col.fill(res, r, action_names)
             rows.append(row)
         return rows
 
     def lane_done():
         cores.release()
-        if agent_policy:
-            lane_selectors.video = lane_selectors.s = None
+        job.lane.video = job.lane.selector = None
 
     rows = run_lanes(root, imset, mine, lanes, work, device, stats, per_video=multi_object, share_frames=share_frames, lane_done=lane_done)
-    if stats is not None:
-        cores.add_to(stats)
-    allrows = shard.gather_rows(np.stack(rows) if rows else np.zeros((0, width), np.float32), width)
+    cores.add_to(stats)
+    allrows, ordered = gather_sorted(rows, width)
     if rank == 0 and out_csv:
         os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
-        order = np.lexsort((allrows[:, 1], allrows[:, 0]))
         with open(out_csv, "w", newline="") as f:
             wr = csv.writer(f)
-            wr.writerow(["video", "mu_metric", "annotation_time", "round"] + (["rl_values"] if agent_policy else [])
-                        + (["annotation_actions"] if typed or agent_policy else []))
-            for row in allrows[order]:
-                if agent_policy:
-                    wr.writerow([ds.object_names[int(row[0])], float(row[2]), float(row[3]), int(row[1]), float(row[-1]), action_names[int(row[-2])]])
-                    continue
-                if typed:                                          # click costs are fractions of a second
-                    wr.writerow([ds.object_names[int(row[0])], float(row[2]), float(row[3]), int(row[1]), action_names[int(row[-1])]])
-                    continue
-                wr.writerow([ds.object_names[int(row[0])], float(row[2]), int(row[3]), int(row[1])])
+            wr.writerow(["video", "mu_metric", "annotation_time", "round"] + [col.name for col in spec.tail])
+            for row in ordered:
+                wr.writerow([ds.object_names[int(row[0])], float(row[2]), spec.seconds(row[3]), int(row[1])]
+                            + [col.cell(row[-1 - j], action_names) for j, col in enumerate(spec.tail)])
     return allrows
 
 
@@ -486,7 +492,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", required=True)
     ap.add_argument("--imset", required=True)
-    ap.add_argument("--policy", default="oracle_mask", choices=POLICIES + TYPED_POLICIES + AGENT_POLICIES)
+    ap.add_argument("--policy", default="oracle_mask", choices=tuple(POLICY_TABLE))
     ap.add_argument("--annotation-types", nargs="+", default=None, metavar="TYPE", help="the mixed-annotation policies (" + ", ".join(TYPED_POLICIES)
                     + "): 'click', 'bbox', 'mask' or '<N>clicks'; one type for rand_type, several for the others")
     ap.add_argument("--annotator", default="component", choices=ANNOTATORS, help="the segmenter behind clicks and boxes: 'component' is a deterministic "
@@ -507,46 +513,29 @@ def main():
     ap.add_argument("--km", type=float, default=None, metavar="SIGMA", help="kernelized memory read: standard deviation (1/16-scale positions) of the Gaussian "
                     "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
     a = ap.parse_args()
-    if a.policy in AGENT_POLICIES and a.annotation_types:
+    spec = POLICY_TABLE[a.policy]
+    typed = "annotation_types" in spec.needs
+    if a.annotation_types and "agent" in spec.needs:
         ap.error(f"{a.policy} takes no --annotation-types: its agent chooses between '3clicks' and 'mask', as the reference's")
-    if a.policy in TYPED_POLICIES:
-        if a.multi_object:
-            ap.error(f"{a.policy} is a one-object policy: --multi-object supports {', '.join(MULTI_OBJECT_POLICIES)}")
-        if not a.annotation_types:
-            ap.error(f"{a.policy} needs --annotation-types")
-    import torch.distributed as dist
-
+    if typed and a.multi_object:
+        ap.error(f"{a.policy} is a one-object policy: --multi-object supports {', '.join(MULTI_OBJECT_POLICIES)}")
+    if typed and not a.annotation_types:
+        ap.error(f"{a.policy} needs --annotation-types")
     from . import synth
-    from .params import FusionNet, PropagationNetwork
-    torch.set_grad_enabled(False)
-    shard.init_from_env()                                  # one process per GPU; RCCL unless STCN_DIST_BACKEND says otherwise
-    prop, fuse, qnet, agent = PropagationNetwork(top_k=a.top_k, km=a.km), FusionNet(), None, None
-    if a.policy in ("qnet_mask",) + AGENT_POLICIES:
+    prop, fuse = load_networks(a)
+    qnet = agent = None
+    if "qnet" in spec.needs:
         from .qnet import QualityNet
         qnet = QualityNet()
-    if a.synthetic_weights:
-        prop.load_state_dict(synth.recipe_state_dict(prop))
-        fuse.load_state_dict(synth.recipe_state_dict(fuse))
-        if qnet is not None:
-            qnet.load_state_dict(synth.recipe_state_dict(qnet, seed=3))
-    else:
-        prop.load_state_dict(torch.load(a.prop_weights, map_location="cpu"))
-        fuse.load_state_dict(torch.load(a.fusion_weights, map_location="cpu"))
-        if qnet is not None:
-            qnet.load_state_dict(torch.load(a.qnet_weights, map_location="cpu"))
-    if qnet is not None:
+        qnet.load_state_dict(synth.recipe_state_dict(qnet, seed=3) if a.synthetic_weights else torch.load(a.qnet_weights, map_location="cpu"))
         qnet = qnet.cuda().eval()
-    if a.policy in AGENT_POLICIES:
+    if "agent" in spec.needs:
         from .agent import ActorCritic, PPOAgent
         agent = (PPOAgent(state_dict=synth.recipe_state_dict(ActorCritic(), seed=5)) if a.synthetic_weights else PPOAgent(model_path=a.agent_weights))
-    typed = a.policy in TYPED_POLICIES
     out = os.path.join("Experiments", a.db, "_".join([a.policy] + (sorted(a.annotation_types) if typed else [])) + ".csv")
-    rows = run(a.root, a.imset, out, prop.eval(), fuse.eval(), a.policy, a.rounds, qnet=qnet, lanes=a.lanes, multi_object=a.multi_object,
-               share_frames=not a.no_share_frames, annotator=a.annotator if typed or agent else None, annotation_types=a.annotation_types, agent=agent)
-    if not dist.is_initialized() or dist.get_rank() == 0:
-        print(f"{len(rows)} rounds -> {out}")
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    rows = run(a.root, a.imset, out, prop, fuse, a.policy, a.rounds, qnet=qnet, lanes=a.lanes, multi_object=a.multi_object,
+               share_frames=not a.no_share_frames, annotator=a.annotator if "annotator" in spec.needs else None, annotation_types=a.annotation_types, agent=agent)
+    report_and_leave(f"{len(rows)} rounds -> {out}")
 
 
 if __name__ == "__main__":

@@ -3,7 +3,7 @@
 Own counterpart of the reference driver ``generate_fq_dataset.py:60-86`` and what it calls - the clip loader
 ``datasets/annotation_dataset.py:80-132`` (one sample per (video, object), ImageNet normalisation
 ``datasets/range_transform.py:3-6``), the oracle policy ``interactions/mask.py:113-156`` (8 rounds: annotate
-the worst frame by J with its ground-truth mask), the per-frame evaluation ``interactions/eval.py:27-81`` and
+the worst frame by J with its ground-truth mask; ``oracle_rounds``, a record for the session loop of ``eva_vos_amd/sessions.py``) and
 the writer ``util/fq_dataset.py:50-91`` (224x224 nearest-resized masks as PNG + a CSV of
 ``state_name, ious, selected_frame``).  Differences by design:
 
@@ -33,10 +33,10 @@ import torch
 from PIL import Image
 
 from . import metrics, shard
+from .sessions import NO_OBJECT, SessionPolicy, annotation_session, frame_quality  # noqa: F401  (frame_quality: callers find it here too)
 
 MEAN = np.array([0.485, 0.456, 0.406], np.float32)
 STD = np.array([0.229, 0.224, 0.225], np.float32)
-NO_OBJECT = 20.0          # the reference's token for frames without the object (interactions/eval.py:67)
 
 
 # ------------------------------------------------------------------------------------------------ data
@@ -341,8 +341,7 @@ class LaneCores:
         self.local.core = None
 
     def add_to(self, stats: dict):
-        for k_ in ("engines_created", "key_frames_encoded"):
-            stats[k_] = stats.get(k_, 0) + getattr(self, k_)
+        add_stats(stats, {k_: getattr(self, k_) for k_ in ("engines_created", "key_frames_encoded")})
 
 
 def run_lanes(root: str, imset: str, mine, lanes: int, work, device: str = "cuda", stats: dict = None, per_video: bool = False,
@@ -400,6 +399,41 @@ def run_lanes(root: str, imset: str, mine, lanes: int, work, device: str = "cuda
         return [r for part in ex.map(lane, range(lanes)) for r in part]
 
 
+def rank_samples(ds: "ClipDataset", share_frames: bool, multi_object: bool = False):
+    """(this process's rank, the sorted samples of `ds` that are its share): an LPT schedule over the ranks by frame count.
+    ``share_frames``: videos are dealt whole - the objects of a video share an engine; else samples are dealt one by one (adjacent objects still
+    share a decode), a per-video sample of the multi-object mode weighing frames x objects."""
+    import torch.distributed as dist
+    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+    if share_frames:
+        parts = shard.lpt_assign_grouped([s[2] for s in ds.samples], [s[0] for s in ds.samples], world)
+    else:
+        parts = shard.lpt_assign([s[2] * (s[1] if multi_object else 1) for s in ds.samples], world)
+    return rank, sorted(parts[rank])
+
+
+def lane_cores(core_class, prop_net, fuse_net, lanes: int, share_frames: bool, multi_object: bool = False) -> LaneCores:
+    """The LaneCores of a driver run: ``core_class`` (InferenceCore, as the caller sees it) over the sample's clip, with all the objects of a
+    per-video sample or with one."""
+    return LaneCores(lambda sample: core_class(prop_net, fuse_net, sample["rgb"], sample["num_objects"] if multi_object else 1,
+                                               engine_options=lane_engine_options(lanes)), share_frames)
+
+
+def add_stats(stats: dict, more: dict) -> None:
+    """Add a session's counters and seconds to the run's `stats` (None: nothing is kept); the lanes share the dict."""
+    if stats is not None:
+        with _STATS_LOCK:
+            for k_, v_ in more.items():
+                stats[k_] = stats.get(k_, 0) + v_
+
+
+def gather_sorted(rows: list, width: int):
+    """The one collective of a run: every rank's rows, gathered on every rank (shard.gather_rows) - and the same rows in the order the CSV
+    lists them, by sample id and round."""
+    allrows = shard.gather_rows(np.stack(rows) if rows else np.zeros((0, width), np.float32), width)
+    return allrows, allrows[np.lexsort((allrows[:, 1], allrows[:, 0]))]
+
+
 def make_synthetic_tree(root: str, videos: Dict[str, tuple], seed: int = 0) -> str:
     """Write a tiny DAVIS-layout dataset (for tests / smoke runs).  videos: name -> (T, H, W, n_objects)."""
     from . import synth
@@ -426,126 +460,18 @@ def make_synthetic_tree(root: str, videos: Dict[str, tuple], seed: int = 0) -> s
 
 
 # ------------------------------------------------------------------------------------------------ policy
-def frame_quality(processor, gt_thw: torch.Tensor, interacted: List[int], metric: str = "j_and_f"):
-    """``eval_processor_metric`` (interactions/eval.py:27-81) for mask annotations: per-frame J or J&F of the engine's
-    masks against the ground truth, annotated frames counting with their GT mask (:57-60), NO_OBJECT token for empty GT.
-    Returns (mean over frames with an object, generated masks uint8 [T,H,W] on the device, quality[T])."""
-    lw, uw, lh, uh = processor.pad
-    seg = processor.masks[:, 0, lh:processor.nh - uh, lw:processor.nw - uw] > 0
-    gtb = gt_thw > 0.5
-    gen = seg.clone()
-    if interacted:
-        gen[interacted] = gtb[interacted]
-    rows = metrics.sequence_scores_gpu(gtb, gen, j_only=metric == "j")      # the boundary measure only when it is asked for
-    q = rows[:, 0 if metric == "j" else 2].copy()
-    empty = (gtb.flatten(1).sum(1) == 0).cpu().numpy()
-    mu = float(np.mean(q[~empty])) if (~empty).any() else float("nan")
-    q[empty] = NO_OBJECT
-    return mu, gen.to(torch.uint8), q
-
-
-def per_frame_j(processor, gt_dev: torch.Tensor, interacted: List[int]) -> tuple:
-    """J per frame on the GPU - the FQ policy selects by J (interactions/mask.py:113-146).  Returns (quality[T], generated masks uint8 [T,H,W])."""
-    _, gen, q = frame_quality(processor, gt_dev, interacted, "j")
-    return q, gen
-
-
-def annotation_session(processor, scorer, T: int, rounds: int, annotate, choose, keep_gen: bool = True, stats: dict = None):
-    """The annotation-session loop of every mask policy (interactions/mask.py:10-39,113-156): round r annotates frame ``frames[r - 1]``
-    (the first one frame 0), propagates, scores the round on the device (``scorer``: a metrics.RoundScorer) and appends the frame to
-    annotate next.  ``annotate(f)`` hands the annotation of frame f to ``processor.interact``; ``choose(worst, gen, frames)`` is the policy:
-    the next frame, given the scorer's arg-min, the evaluated masks and the frames annotated so far.  A round is skipped when the clip has no
-    more frames than rounds (``r >= T``) or, after the first scored round, when nothing is left to annotate (not_avail_frames,
-    interactions/eval.py:84-89: every frame is annotated or carries the NO_OBJECT token).  ``stats`` (optional dict): the frames the engine
-    really visited (``propagated_frames``) and the ``interactions`` are added to it.  Returns (frames, gens): every frame chosen, frame 0
-    first - one more than the rounds scored -, and the evaluated masks of every scored round (distinct tensors only with ``keep_gen``)."""
-    valid = set(np.where(~scorer.empty_host)[0].tolist())       # frames that can be annotated at all
-    frames, gens = [0], []
-    for r in range(1, rounds + 1):
-        if r >= T or (gens and not (valid - set(frames))):
-            continue
-        annotate(frames[r - 1])
-        if stats is not None:
-            stats["propagated_frames"] = stats.get("propagated_frames", 0) + processor.stats()["frames"]
-            stats["interactions"] = stats.get("interactions", 0) + 1
-        worst, gen = scorer.score(processor, frames, keep_gen=keep_gen)
-        gens.append(gen)
-        frames.append(choose(worst, gen, frames))
-    return frames, gens
-
-
-def new_frame_annotations(T: int) -> list:
-    """pf_annots of ``initialize`` (interactions/eval.py:107-115): per frame the actions taken on it and the prompts to continue from."""
-    return [dict(annotations=[], click_labels=None, click_coords=None, bbox=None, sam_logits=None) for _ in range(T)]
-
-
-def typed_annotation_session(processor, scorer, T: int, rounds: int, gt, choose_action, next_frame, stats: dict = None, select=None):
-    """The session loop of the mixed-annotation policies (interactions/mulitple_annotations.py:104-283; ``eva_vos``, :307-378, is the same
-    loop with an agent behind ``choose_action``).  Round 1 annotates frame 0 with its mask at 80 s.  Round r > 1 annotates ``frames[-1]``:
-    ``choose_action(frame, gen, frame_annots) -> (mask, cost, action, logits, clicks, labels, bbox)`` is the policy's annotation of it given the
-    masks evaluated last (``gen`` uint8 [T,H,W] on the device); ``store_action_data`` (:88-101): the action 'mask' makes the frame type 1
-    and interacts with the ground truth, every other action makes it type 2, hands the annotator's mask to ``scorer.set_annotation`` and
-    keeps the prompts for a later annotation of the same frame.  The engine propagates (``processor.interact``), ``scorer`` (a
-    metrics.TypedRoundScorer) evaluates, and ``next_frame(worst, types) -> frame or None`` picks the next one - frames REPEAT: a type-2 frame
-    stays selectable until it gets a mask; ``select(worst, types, gen, frames)``, when given, is called in its place: a selection that reads
-    the evaluated masks and the frames chosen so far (``eva_vos``'s QNet).  Skip rules (:117-123): ``r >= T`` with every frame at quality 1, every frame annotated with a mask
-    (types: none but 1 left), or - after the first round - no frame left that is neither chosen nor without the object (not_avail_frames).
-    ``gt``: [T,1,H,W] on the device.  Returns dict(frames, types, costs, actions): per scored round the annotated frame, its type (1 / 2), the
-    seconds, the action; plus ``pending``: the frame chosen last, or None."""
-    empty = scorer.empty_host
-    valid = set(np.where(~empty)[0].tolist())
-    types = np.zeros(T, np.int64)
-    frames, done_types, costs, actions = [0], [], [], []
-    annots = new_frame_annotations(T)
-    gen, fully, pending = None, False, 0
-    for r in range(1, rounds + 1):
-        if fully or pending is None or (r >= T and gen is not None and float(np.min(scorer.qualities()[-1])) == 1.0):
-            continue
-        if gen is not None and not (valid - set(frames)):
-            continue
-        frame = pending
-        if r > 1:
-            mask, cost, action, logits, clicks, labels, bbox = choose_action(frame, gen, annots[frame])
-        else:
-            mask, cost, action = None, 80, "mask"
-        if action == "mask":
-            types[frame] = 1
-            interaction = gt[frame][None]
-        else:
-            types[frame] = 2
-            interaction = mask.reshape(gt[frame].shape).float()[None]
-            scorer.set_annotation(frame, mask)
-            annots[frame].update(click_labels=labels, click_coords=clicks, bbox=bbox, sam_logits=logits)
-        annots[frame]["annotations"].append(action)
-        processor.interact(interaction, frame, download=False)
-        if stats is not None:
-            stats["propagated_frames"] = stats.get("propagated_frames", 0) + processor.stats()["frames"]
-            stats["interactions"] = stats.get("interactions", 0) + 1
-        done_types.append(int(types[frame]))
-        worst, gen = scorer.score(processor, frames, keep_gen=False, types=done_types)
-        costs.append(cost)
-        actions.append(action)
-        fully = not (types != 1).any()
-        pending = next_frame(worst, types) if select is None else select(worst, types, gen, frames)
-        if pending is not None:
-            frames.append(int(pending))
-    n = len(costs)
-    return dict(frames=frames[:n], types=done_types, costs=costs, actions=actions, pending=pending if len(frames) > n else None)
-
-
 def oracle_rounds(processor, sample, rounds: int = 8, stats: dict = None):
     """The oracle annotation policy of the FQ dataset (interactions/mask.py:113-156): annotate the worst frame by J with its ground-truth
-    mask.  `stats` (optional dict, one per caller thread): see annotation_session.
+    mask.  `stats` (optional dict, one per caller thread): see sessions.annotation_session.
     Round 6: the evaluation of a round stays on the device (metrics.RoundScorer: compose + J counts + fp64 quality + arg-min in one enqueue);
     one int per round crosses PCIe, the per-frame J rows of all rounds are fetched once at the end.  Same values, same selection as
-    per_frame_j + numpy.argmin (tests/test_gpu_driver_golden.py).  Returns ([(selected frame, quality[T]) per round], gens)."""
+    sessions.frame_quality + numpy.argmin (tests/test_gpu_driver_golden.py).  Returns ([(selected frame, quality[T]) per round], gens)."""
     gt = sample["gt"][0].to(processor.prob.device)              # [T,1,H,W]
     scorer = metrics.RoundScorer(gt[:, 0], "j", max_rounds=max(rounds, 1), no_object=NO_OBJECT)
-    frames, gens = annotation_session(processor, scorer, sample["num_frames"], rounds,
-                                      lambda f: processor.interact(gt[f][None], f, download=False),       # [1,1,H,W] mask of the annotated frame
-                                      lambda worst, gen, frames: worst, stats=stats)
+    policy = SessionPolicy(mask_of=lambda f: gt[f][None], choose_frame=lambda worst, types, gen, frames: worst, keep_gen=True)
+    ses = annotation_session(processor, scorer, sample["num_frames"], rounds, policy, stats)
     q = scorer.qualities()
-    return [(w, q[i]) for i, w in enumerate(frames[1:])], gens
+    return [(w, q[i]) for i, w in enumerate(ses["chosen"][1:])], ses["gens"]
 
 
 # ------------------------------------------------------------------------------------------------ output
@@ -571,50 +497,14 @@ def write_png(path: str, a: np.ndarray, level: int = 1) -> None:
                 chunk(b"IDAT", zlib.compress(raw.tobytes(), level)) + chunk(b"IEND", b""))
 
 
-
-def save_state_masks(gen: torch.Tensor, out_dir: str, pool=None):
-    """224x224 nearest-neighbour PNGs like util/fq_dataset.py:64-84 (mask_to_224).  The resize runs on the device; with
-    `pool` (a ThreadPoolExecutor) the PNG encoding + file writes of the state happen on host threads while the GPU
-    propagates the next round (zlib and file I/O release the GIL); returns the future, or None when done inline.
-    Round 6: with a pool the download does not stop the lane either - the 224x224 frames go to pinned memory asynchronously and the
-    WRITER thread waits for the copy (an event), not the thread that drives the GPU."""
-    small = torch.nn.functional.interpolate(gen[:, None].float(), size=(224, 224), mode="nearest")[:, 0]
-    small = (small * 255).to(torch.uint8)
-    if pool is None or not small.is_cuda:
-        frames, ready = small.cpu().numpy(), None
-    else:
-        host = torch.empty(small.shape, dtype=torch.uint8, pin_memory=True)
-        host.copy_(small, non_blocking=True)
-        ready = torch.cuda.Event(blocking=True)
-        ready.record()
-        small.record_stream(torch.cuda.current_stream())
-        frames = host.numpy()
-
-    def write():
-        if ready is not None:
-            ready.synchronize()
-        os.makedirs(out_dir, exist_ok=True)
-        for t, m in enumerate(frames):
-            write_png(os.path.join(out_dir, f"{t:05d}.png"), m)
-
-    if pool is None:
-        write()
-        return None
-    return pool.submit(write)
-
-
-def save_rgb_frames(rgb: torch.Tensor, out_dir: str, pool=None):
-    """RGBFrames/224/<video>/%05d.png like util/fq_dataset.py:26-47 (``save_frames``): each normalised frame is resized to
-    224x224 (bicubic, antialias), min-max normalised PER FRAME (``im_normalize``) and written as 8-bit RGB - the inputs of
-    the reference's QNet training set.  rgb: [T,3,H,W] float (ImageNet-normalised, host or device); the resize runs where
-    the tensor lives, the PNG encoding on `pool` threads when given."""
-    small = torch.nn.functional.interpolate(rgb.float(), size=(224, 224), mode="bicubic", align_corners=False, antialias=True)
-    lo = small.amin((1, 2, 3), keepdim=True)
-    hi = small.amax((1, 2, 3), keepdim=True)
-    dev8 = ((small - lo) / (hi - lo).clamp_min(1e-8) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+def _write_frames(dev8: torch.Tensor, out_dir: str, pool=None):
+    """uint8 frames [T,H,W] or [T,H,W,3] -> out_dir/%05d.png.  With `pool` (a ThreadPoolExecutor) the PNG encoding + file writes happen on
+    host threads while the GPU propagates the next round (zlib and file I/O release the GIL); returns the future, or None when done inline.
+    Round 6: with a pool the download does not stop the lane either - the frames go to pinned memory asynchronously and the WRITER thread
+    waits for the copy (an event), not the thread that drives the GPU."""
     if pool is None or not dev8.is_cuda:
         frames, ready = dev8.cpu().numpy(), None
-    else:                                                           # as save_state_masks: the WRITER waits for the download, not the lane
+    else:
         host = torch.empty(dev8.shape, dtype=torch.uint8, pin_memory=True)
         host.copy_(dev8, non_blocking=True)
         ready = torch.cuda.Event(blocking=True)
@@ -635,6 +525,24 @@ def save_rgb_frames(rgb: torch.Tensor, out_dir: str, pool=None):
     return pool.submit(write)
 
 
+def save_state_masks(gen: torch.Tensor, out_dir: str, pool=None):
+    """224x224 nearest-neighbour PNGs like util/fq_dataset.py:64-84 (mask_to_224).  The resize runs on the device; `pool` and the return
+    value: see _write_frames."""
+    small = torch.nn.functional.interpolate(gen[:, None].float(), size=(224, 224), mode="nearest")[:, 0]
+    return _write_frames((small * 255).to(torch.uint8), out_dir, pool)
+
+
+def save_rgb_frames(rgb: torch.Tensor, out_dir: str, pool=None):
+    """RGBFrames/224/<video>/%05d.png like util/fq_dataset.py:26-47 (``save_frames``): each normalised frame is resized to
+    224x224 (bicubic, antialias), min-max normalised PER FRAME (``im_normalize``) and written as 8-bit RGB - the inputs of
+    the reference's QNet training set.  rgb: [T,3,H,W] float (ImageNet-normalised, host or device); the resize runs where
+    the tensor lives, the PNG encoding on `pool` threads when given (_write_frames)."""
+    small = torch.nn.functional.interpolate(rgb.float(), size=(224, 224), mode="bicubic", align_corners=False, antialias=True)
+    lo = small.amin((1, 2, 3), keepdim=True)
+    hi = small.amax((1, 2, 3), keepdim=True)
+    return _write_frames(((small - lo) / (hi - lo).clamp_min(1e-8) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous(), out_dir, pool)
+
+
 def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, save_masks: bool = True,
         device: str = "cuda", lanes: int = 2, stats: dict = None, share_frames: bool = True):
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
@@ -644,21 +552,13 @@ def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, sa
     `share_frames`: the sessions of a video's objects run one after the other on ONE engine that keeps the clip and its frame features
     between them (LaneCores) - videos, not samples, are dealt to ranks and lanes.  Same rows, same files; False: a fresh engine and a
     fresh upload per sample, samples dealt one by one."""
-    import torch.distributed as dist
     from concurrent.futures import ThreadPoolExecutor
 
     from mivos.inference_core import InferenceCore
-    rank = dist.get_rank() if dist.is_initialized() else 0
-    world = dist.get_world_size() if dist.is_initialized() else 1
     ds = ClipDataset(root, imset)
-    t_max = max(s[2] for s in ds.samples)
-    frames = [s[2] for s in ds.samples]
-    if share_frames:
-        mine = sorted(shard.lpt_assign_grouped(frames, [s[0] for s in ds.samples], world)[rank])     # the objects of a video share an engine
-    else:
-        mine = sorted(shard.lpt_assign(frames, world)[rank])     # adjacent objects share a decode
-    cores = LaneCores(lambda sample: InferenceCore(prop_net, fuse_net, sample["rgb"], 1, engine_options=lane_engine_options(lanes)), share_frames)
-    width = 4 + t_max
+    rank, mine = rank_samples(ds, share_frames)
+    cores = lane_cores(InferenceCore, prop_net, fuse_net, lanes, share_frames)
+    width = 4 + max(s[2] for s in ds.samples)
     writers = ThreadPoolExecutor(8) if save_masks else None           # zlib releases the GIL: the encoders really run beside the lanes
     pending = []
 
@@ -680,10 +580,7 @@ def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, sa
         states, gens = oracle_rounds(proc, sample, rounds, mine_stats)
         cores.done(proc)
         if stats is not None:
-            mine_stats["session_s"] = time.perf_counter() - t_c
-            with rgb_lock:
-                for k_, v_ in mine_stats.items():
-                    stats[k_] = stats.get(k_, 0) + v_
+            add_stats(stats, dict(mine_stats, session_s=time.perf_counter() - t_c))
         sid = 1
         for r, ((worst, q), gen) in enumerate(zip(states, gens)):
             if float(q[worst]) == NO_OBJECT:
@@ -698,8 +595,7 @@ def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, sa
         return rows
 
     rows = run_lanes(root, imset, mine, lanes, work, device, stats, share_frames=share_frames, lane_done=cores.release)
-    if stats is not None:
-        cores.add_to(stats)
+    cores.add_to(stats)
     t_p = time.perf_counter()
     for f in pending:
         f.result()                                         # surface write errors; all PNGs are on disk before the CSV
@@ -707,19 +603,40 @@ def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, sa
         stats["wait_writers_s"] = round(time.perf_counter() - t_p, 4)
     if writers is not None:
         writers.shutdown()
-    allrows = shard.gather_rows(np.stack(rows) if rows else np.zeros((0, width), np.float32), width)
+    allrows, ordered = gather_sorted(rows, width)
     if rank == 0:
         os.makedirs(out, exist_ok=True)
-        order = np.lexsort((allrows[:, 1], allrows[:, 0]))
         # res_<imset>.csv, columns as generate_fq_dataset.py:48-52,85-86 (the ious cell holds the per-frame list)
         imset_str = os.path.splitext(os.path.basename(imset))[0]
         with open(os.path.join(out, f"res_{imset_str}.csv"), "w", newline="") as f:
             wr = csv.writer(f)
             wr.writerow(["state_name", "ious", "selected_frame"])
-            for row in allrows[order]:
+            for row in ordered:
                 n = int(row[3])
                 wr.writerow([f"{ds.name(int(row[0]))}_round_{int(row[1])}", [float(v) for v in row[4:4 + n]], int(row[2])])
     return allrows
+
+
+def load_networks(a):
+    """The start of either driver's main(): gradients off, this process bound to its GPU and joined to the process group (one process per GPU;
+    RCCL unless STCN_DIST_BACKEND says otherwise), and the two networks, in eval mode, with the weights the command line `a` names."""
+    from . import synth
+    from .params import FusionNet, PropagationNetwork
+    torch.set_grad_enabled(False)
+    shard.init_from_env()
+    prop, fuse = PropagationNetwork(top_k=a.top_k, km=a.km), FusionNet()
+    for net, path in ((prop, a.prop_weights), (fuse, a.fusion_weights)):
+        net.load_state_dict(synth.recipe_state_dict(net) if a.synthetic_weights else torch.load(path, map_location="cpu"))
+    return prop.eval(), fuse.eval()
+
+
+def report_and_leave(message: str) -> None:
+    """The end of it: rank 0 says where the output is, the process group is left."""
+    import torch.distributed as dist
+    if not dist.is_initialized() or dist.get_rank() == 0:
+        print(message)
+    if dist.is_initialized():
+        dist.destroy_process_group()
 
 
 def main():
@@ -738,24 +655,9 @@ def main():
     ap.add_argument("--km", type=float, default=None, metavar="SIGMA", help="kernelized memory read: standard deviation (1/16-scale positions) of the Gaussian "
                     "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
     a = ap.parse_args()
-    import torch.distributed as dist
-
-    from . import synth
-    from .params import FusionNet, PropagationNetwork
-    torch.set_grad_enabled(False)
-    shard.init_from_env()                                  # one process per GPU; RCCL unless STCN_DIST_BACKEND says otherwise
-    prop, fuse = PropagationNetwork(top_k=a.top_k, km=a.km), FusionNet()
-    if a.synthetic_weights:
-        prop.load_state_dict(synth.recipe_state_dict(prop))
-        fuse.load_state_dict(synth.recipe_state_dict(fuse))
-    else:
-        prop.load_state_dict(torch.load(a.prop_weights, map_location="cpu"))
-        fuse.load_state_dict(torch.load(a.fusion_weights, map_location="cpu"))
-    rows = run(a.root, a.imset, a.out, prop.eval(), fuse.eval(), a.rounds, lanes=a.lanes, share_frames=not a.no_share_frames)
-    if not dist.is_initialized() or dist.get_rank() == 0:
-        print(f"{len(rows)} states -> {os.path.join(a.out, 'res_' + os.path.splitext(os.path.basename(a.imset))[0] + '.csv')}")
-    if dist.is_initialized():
-        dist.destroy_process_group()
+    prop, fuse = load_networks(a)
+    rows = run(a.root, a.imset, a.out, prop, fuse, a.rounds, lanes=a.lanes, share_frames=not a.no_share_frames)
+    report_and_leave(f"{len(rows)} states -> {os.path.join(a.out, 'res_' + os.path.splitext(os.path.basename(a.imset))[0] + '.csv')}")
 
 
 if __name__ == "__main__":

@@ -3,14 +3,15 @@ agent's draws, the argument checks of ``stcn_masks_resize_nearest``, the stand-i
 restatement of the reference's ``eva_vos`` (interactions/mulitple_annotations.py:286-378) on fakes that record every call."""
 import ctypes as C
 import os
-import types
 
 import numpy as np
 import pytest
 import torch
 
-from eva_vos_amd import _lib, annotate, eval_driver, fq_driver, metrics, synth
+from eva_vos_amd import _lib, annotate, eval_driver, fq_driver, sessions, synth
 from eva_vos_amd import agent as A
+from session_fakes import Agent, Annotator, Proc, Scorer, Selector
+from session_fakes import clip as _clip, gen_masks as _gen, quality as _quality
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "agent.npz")
 NO = fq_driver.NO_OBJECT
@@ -181,85 +182,6 @@ def test_the_embedding_is_taken_from_the_controllers_own_predictor_or_refused():
 
 
 # ------------------------------------------------------------------------------------------------ the loop
-def _quality(cur_types, empty):
-    """The fake evaluation both loops use: 1 on a frame annotated with its mask, 0.5 elsewhere, the token on a frame without the object."""
-    q = np.where(np.asarray(cur_types) == 1, 1.0, 0.5)
-    q[empty] = NO
-    return q
-
-
-def _gen(T, r):
-    return torch.full((T, 2, 2), r, dtype=torch.uint8)
-
-
-class Proc:
-    def __init__(self, log):
-        self.log, self.prob, self.calls = log, types.SimpleNamespace(device=torch.device("cpu")), 0
-
-    def interact(self, mask, f, **kw):
-        self.calls += 1
-        self.log.append(("interact", int(f), list(mask.shape), mask.flatten().int().tolist()))
-
-    def stats(self):
-        return {"frames": 3}
-
-
-class Scorer:
-    """``TypedRoundScorer``'s interface over ``_quality``."""
-
-    def __init__(self, gt_thw, log):
-        self.T, self.log, self.rows = gt_thw.shape[0], log, []
-        self.empty_host = (gt_thw.flatten(1).sum(1) == 0).numpy()
-
-    def set_annotation(self, frame, mask):
-        self.log.append(("annotation", int(frame), mask.flatten().int().tolist()))
-
-    def score(self, processor, annotated_frames, keep_gen=True, incremental=True, types=None):
-        cur = metrics._current_types(self.T, annotated_frames, types)
-        self.rows.append(_quality(cur, self.empty_host))
-        return int(np.argmin(self.rows[-1])), _gen(self.T, len(self.rows))
-
-    def qualities(self):
-        return np.stack(self.rows)
-
-
-class Annotator:
-    def __init__(self, log):
-        self.log = log
-
-    def image_embedding(self, im, gt_mask):
-        self.log.append(("embedding", list(im.shape), gt_mask.flatten().int().tolist()))
-        return "embedding"
-
-    def annotate(self, annot_type, gt_mask, im=None, mivos_mask=None, frame_annots=None, empty=None):
-        self.log.append(("annotate", annot_type, mivos_mask.flatten().int().tolist(), list(frame_annots["annotations"]), frame_annots["click_coords"]))
-        if annot_type == "mask":
-            return gt_mask, 80, 1, None, None, None, None
-        return 1 - gt_mask, 4.5, 0.7, "logits", "clicks", "labels", None         # a mask that is not the ground truth
-
-
-class Agent:
-    def __init__(self, script, log):
-        self.script, self.log = list(script), log
-
-    def act(self, x_img, x_mask, generator=None):
-        action, value = self.script.pop(0)
-        self.log.append(("act", x_img, x_mask, generator))
-        return action, torch.tensor([[value]])
-
-
-class Selector:
-    def __init__(self, script, log):
-        self.script, self.log = list(script), log
-
-    def masks_to_input(self, gen, frames=None):
-        return ("input", int(gen[0, 0, 0]), list(frames))
-
-    def select(self, gen, interacted):
-        self.log.append(("select", int(gen[0, 0, 0]), [int(f) for f in interacted]))
-        return self.script.pop(0)
-
-
 def reference_eva_vos(T, rounds, gt, images, annotator, rl_agent, selector, log):
     """``eva_vos`` with ``rl_agent_annotate`` and ``store_action_data`` (interactions/mulitple_annotations.py:286-378, 88-101), restated line by
     line over the fakes: ``eval_processor_metric`` is ``_quality`` of the frame types, ``qnet_frame_selection`` is ``selector.select``."""
@@ -323,15 +245,6 @@ def reference_eva_vos(T, rounds, gt, images, annotator, rl_agent, selector, log)
         annotations_actions.append(ann_action)
         round_metrics.append(metric)
     return mu_metrics, annotation_times, rl_values, annotations_actions, round_metrics, frames_list[:-1]
-
-
-def _clip(T, empty_frames):
-    gt = torch.zeros((T, 1, 2, 2))
-    for t in range(T):
-        gt[t, 0, 0, t % 2] = 1
-    for t in empty_frames:
-        gt[t] = 0
-    return gt, torch.zeros((1, T, 3, 2, 2))
 
 
 # T, rounds, frames without the object, the selector's answers, the agent's (action, value) answers
@@ -405,9 +318,10 @@ def test_the_session_loop_without_select_calls_next_frame_as_before():
     gt, _ = _clip(3, [])
     log, calls = [], []
 
-    def next_frame(worst, types_):
+    def next_frame(worst, types_, gen, frames):
         calls.append((worst, types_.tolist()))
         return None
 
-    ses = fq_driver.typed_annotation_session(Proc(log), Scorer(gt[:, 0], log), 3, 4, gt, None, next_frame)
+    ses = sessions.annotation_session(Proc(log), Scorer(gt[:, 0], log), 3, 4, 
+                                     sessions.SessionPolicy(lambda f: gt[f][None], next_frame, action=lambda *a: pytest.fail("round 2 never starts"), stop_at_T=False))
     assert calls == [(1, [1, 0, 0])] and ses["frames"] == [0] and ses["pending"] is None

@@ -3,13 +3,12 @@
 the objects of a video together, and the drivers' engine reuse on a fake ``InferenceCore`` that logs every call."""
 import ctypes as C
 import random
-import types
 
 import numpy as np
 import pytest
-import torch
 
 from eva_vos_amd import _lib, eval_driver, fq_driver, metrics, shard
+from session_fakes import DriverScorer as _FakeScorer, fake_core_class as _fake_core_class
 
 
 # ------------------------------------------------------------------------------------------------ ABI
@@ -105,50 +104,6 @@ def test_run_lanes_hands_a_video_to_one_lane(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------ drivers on fakes
-class _FakeScorer:
-    """metrics.RoundScorer's surface as the session loop uses it: every frame holds the object, the worst frame is the first one not
-    annotated yet."""
-
-    def __init__(self, gt_thw, metric="j", max_rounds=64, no_object=20.0, num_objects=None):
-        self.T, self.rounds = int(gt_thw.shape[0]), 0
-        self.empty_host = np.zeros(self.T, bool)
-
-    def score(self, processor, annotated_frames, keep_gen=True, incremental=True):
-        self.rounds += 1
-        return min(set(range(self.T)) - set(annotated_frames)), torch.zeros((self.T, 2, 2), dtype=torch.uint8)
-
-    def qualities(self):
-        return np.full((self.rounds, self.T), 0.5)
-
-
-def _fake_core_class(log):
-    class Core:
-        """InferenceCore's surface as the drivers use it.  A frame is key-encoded when an interaction first needs it; the features of a
-        clip survive ``reset(keep_frame_features=True)`` only."""
-
-        def __init__(self, prop_net, fuse_net, images, num_objects, mem_profile=0, mem_freq=5, device="cuda", engine_options=None):
-            self.t = int(images.shape[1])
-            self.images, self.cached, self.key_frames_encoded = images, False, 0
-            self.prob = types.SimpleNamespace(device=torch.device("cpu"))
-            log.append(("new", self.t, int(num_objects), engine_options))
-
-        def interact(self, mask, idx, scribble=False, download=True):
-            if not self.cached:
-                self.key_frames_encoded += self.t
-                self.cached = True
-            log.append(("interact", self.t, int(idx)))
-
-        def reset(self, keep_frame_features=False):
-            log.append(("reset", self.t, keep_frame_features))
-            self.key_frames_encoded = 0
-            self.cached = self.cached and keep_frame_features
-            return self.t if self.cached else 0
-
-        def stats(self):
-            return {"frames": self.t - 1}
-    return Core
-
-
 @pytest.fixture
 def fake_tree(tmp_path, monkeypatch):
     import mivos.inference_core

@@ -405,7 +405,7 @@ def session_parity(prop, fuse, psd, fsd, H, W, T, rounds, mem_freq, eo=None):
     orc = OracleCore(psd, fsd, img, 1, mem_freq=mem_freq)
     core = InferenceCore(prop, fuse, img.cuda(), 1, mem_freq=mem_freq, engine_options=eo)
 
-    def per_frame_j(masks, done):
+    def frame_j(masks, done):
         gen = masks > 0
         gen[done] = gtb[done]
         u, n = (gen | gtb).reshape(T, -1).sum(1), (gen & gtb).reshape(T, -1).sum(1)
@@ -424,7 +424,7 @@ def session_parity(prop, fuse, psd, fsd, H, W, T, rounds, mem_freq, eo=None):
         a_, b_ = got > 0, ref > 0
         fu, fi = (a_ | b_).reshape(T, -1).sum(1), (a_ & b_).reshape(T, -1).sum(1)
         fiou = np.where(fu >= 64, fi / np.maximum(fu, 1), 1.0)
-        q_ref, q_got = per_frame_j(ref, frames[:r + 1]), per_frame_j(got, frames[:r + 1])
+        q_ref, q_got = frame_j(ref, frames[:r + 1]), frame_j(got, frames[:r + 1])
         nxt = int(np.argmin(q_ref))
         fb = np.array([frame_bound(noise, u) for u in fu])
         miou = float((a_ & b_).sum() / max((a_ | b_).sum(), 1))
