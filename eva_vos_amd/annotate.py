@@ -81,21 +81,27 @@ class PromptAnnotator:
 
     def set_image(self, im, gt_mask):
         """annotator.py:30-35: the frame as uint8 [H,W,3] for the predictor; a stand-in that knows the ground truth gets it here."""
+        given = im                                              # what image_embedding(reuse=True) recognises the frame by
         if im is not None and hasattr(im, "detach"):
             a = im.detach().cpu().squeeze().numpy().transpose((1, 2, 0)) * STD + MEAN
             im = (a * 255).astype(np.uint8)
+        self._image_given = None
         self.predictor.reset_image()
         if hasattr(self.predictor, "set_target"):
             self.predictor.set_target(gt_mask)
         self.predictor.set_image(im)
+        self._image_given = given
 
-    def image_embedding(self, im, gt_mask):
+    def image_embedding(self, im, gt_mask, reuse: bool = False):
         """The segmenter's embedding of the frame, the agent's first input (rl_agent_annotate, interactions/mulitple_annotations.py:293-294):
         ``set_image`` as above, then ``get_image_embedding()`` of the predictor or of ``predictor.predictor`` - where the reference's
-        ``SAMController`` keeps SAM's own predictor (sam/sam_controller.py) -> [1,256,64,64]."""
+        ``SAMController`` keeps SAM's own predictor (sam/sam_controller.py) -> [1,256,64,64].  ``reuse``: where the predictor holds this
+        very ``im`` already - the object the last ``set_image`` was given, as after an ``annotate`` with clicks or a box on it - the image
+        is not set again (no second pass of the segmenter's encoder: generate_annotation_dataset.py:120 reads the embedding the action left)."""
         for p in (self.predictor, getattr(self.predictor, "predictor", None)):
             if hasattr(p, "get_image_embedding"):
-                self.set_image(im, gt_mask)
+                if not (reuse and im is not None and getattr(self, "_image_given", None) is im):
+                    self.set_image(im, gt_mask)
                 return p.get_image_embedding()
         raise ValueError(f"eva_vos needs the image embedding its agent reads: {type(self.predictor).__name__} offers no get_image_embedding(), "
                          "neither itself nor through a .predictor attribute (SAMController, ComponentPredictor do)")

@@ -654,6 +654,28 @@ int stcn_masks_resize_nearest(void *stream, const uint8_t *src, int T, int H, in
     return STCN_OK;
 }
 
+// ---- frames as stored images (rgb8.hip): every argument is checked before any device call -------------------------------------------------
+int stcn_frames_to_rgb8(void *stream, const float *clip_dev, int T, int H, int W, const int32_t *frames_dev, int n, void *scratch_dev, uint8_t *out_dev) {
+    const char *who = "stcn_frames_to_rgb8";
+    if (!clip_dev || !scratch_dev || !out_dev) {
+        set_error("%s: null pointer (%s)", who, !clip_dev ? "clip_dev" : !scratch_dev ? "scratch_dev" : "out_dev");
+        return STCN_E_INVALID;
+    }
+    if (n < 0 || n > 65535) { set_error("%s: n = %d frames in one call (0 <= n <= 65535)", who, n); return STCN_E_INVALID; }
+    if (T < 1 || H < 1 || W < 1 || (long)H * W > MAX_FRAME_PIXELS) {
+        set_error("%s: bad clip [%d, 3, %d, %d]: every size is at least 1, H * W at most 2^24", who, T, H, W);
+        return STCN_E_INVALID;
+    }
+    if ((uintptr_t)clip_dev % 4 != 0 || (uintptr_t)scratch_dev % 4 != 0) {
+        set_error("%s: clip_dev=%p and scratch_dev=%p must be 4-byte aligned", who, (const void *)clip_dev, scratch_dev);
+        return STCN_E_INVALID;
+    }
+    if (n == 0) return STCN_OK;
+    frames_to_rgb8_launch(clip_dev, T, H, W, frames_dev, n, scratch_dev, out_dev, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
 int stcn_bench_mfma_rate(void *stream, int ms_target, float *tflops, float *ms_out) {
     if (!tflops || ms_target < 1 || ms_target > 2000) { set_error("stcn_bench_mfma_rate: bad arguments"); return STCN_E_INVALID; }
     hipStream_t s = (hipStream_t)stream;

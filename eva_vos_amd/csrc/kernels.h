@@ -337,6 +337,13 @@ void robot_best_mask_launch(const uint8_t *cand, const uint8_t *target, int M, i
 void masks_resize_nearest_launch(const uint8_t *src, int T, int H, int W, const int *frames, int n, int out_h, int out_w, int channels, float *out,
                                  hipStream_t s);
 
+// ---------------------------------------------------------------- frames as stored images (rgb8.hip)
+// clip fp32 [T,3,H,W] (4-byte aligned, finite) -> out uint8 [n,H,W,3]: per frame (x - min) / max(max - min, 1e-8f) * 255 in correctly rounded
+// fp32, truncated.  frames: device int32 [n] or nullptr = frames 0..n-1; an index outside [0,T) is not read, its image becomes zeros.
+// scratch: n * 8 bytes, 4-byte aligned, initialised by the call.  H * W <= MAX_FRAME_PIXELS, 1 <= n <= 65535 (checked by the caller).
+// Enqueues three launches.
+void frames_to_rgb8_launch(const float *clip, int T, int H, int W, const int *frames, int n, void *scratch, uint8_t *out, hipStream_t s);
+
 // ---------------------------------------------------------------- frame distances (frame_select.hip)
 // dist [T][T] fp64 = squared L2 distances between T vectors of K fp32 values, vector t at x + index.v[t] * stride (16-byte aligned: x and
 // stride multiples of 4 floats, K % 4 == 0, K >= 4, 1 <= T <= FRAME_GRAM_MAX_T).  The Gram matrix is accumulated in fp64 on the matrix cores

@@ -50,13 +50,17 @@ class SessionPolicy:
     round after the first, for a policy that has others than masks (``frame_annots``: pf_annots of ``initialize``, interactions/eval.py:107-115 -
     the actions taken on the frame and the prompts to continue from); None: every round is a mask.
     ``stop_at_T``: which of the reference's two rules ends a session whose rounds outnumber its frames (see ``annotation_session``).
-    ``keep_gen``: the policy keeps the evaluated masks of a round beyond the next one (distinct tensors instead of the scorer's scratch)."""
+    ``keep_gen``: the policy keeps the evaluated masks of a round beyond the next one (distinct tensors instead of the scorer's scratch).
+    ``stop_when_perfect``: the quality rule ends the session at EVERY round, not only from round T on (generate_annotation_dataset.py:109).
+    ``check_available``: the ``not_avail_frames`` skip applies (the loop of generate_annotation_dataset.py has none)."""
     mask_of: Callable
     choose_frame: Callable
     action: Optional[Callable] = None
     stop_at_T: bool = True
     keep_gen: bool = False
     interact_kw: dict = field(default_factory=dict)
+    stop_when_perfect: bool = False
+    check_available: bool = True
 
 
 def annotation_session(processor, scorer, T: int, rounds: int, policy: SessionPolicy, stats: dict = None) -> dict:
@@ -69,6 +73,8 @@ def annotation_session(processor, scorer, T: int, rounds: int, policy: SessionPo
     the next frame - frames may REPEAT: a type-2 frame stays selectable until it gets its mask.
     A round is skipped when no frame is pending, when every frame has its mask, by the policy's stop rule (below), or - after the first
     scored round - when no frame is left that is neither chosen nor without the object (not_avail_frames, interactions/eval.py:84-89).
+    The loop of generate_annotation_dataset.py:108-110 asks for the quality rule at every round and has no not_avail_frames skip:
+    ``stop_when_perfect=True``, ``check_available=False`` (one more download of the quality rows per round).
     ``stats`` (optional dict): the frames the engine really visited (``propagated_frames``) and the ``interactions`` are added to it.
     Returns dict(frames, types, costs, actions, gens: per scored round the annotated frame, its type (1 / 2), the seconds, the action and
     the evaluated masks; pending: the frame chosen last, or None; chosen: frames + the pending one; propagated_frames: what this session
@@ -86,9 +92,9 @@ def annotation_session(processor, scorer, T: int, rounds: int, policy: SessionPo
         # the reference's two stop rules for r >= T
         if r >= T and policy.stop_at_T:                                                             # interactions/mask.py:16
             continue
-        if r >= T and costs and float(np.min(scorer.qualities()[-1])) == 1.0:                       # interactions/mulitple_annotations.py:117
+        if (r >= T or policy.stop_when_perfect) and costs and float(np.min(scorer.qualities()[-1])) == 1.0:     # interactions/mulitple_annotations.py:117
             continue
-        if costs and not (valid - set(frames)):
+        if policy.check_available and costs and not (valid - set(frames)):
             continue
         frame = pending
         if r > 1 and policy.action is not None:

@@ -650,6 +650,18 @@ int stcn_robot_best_mask(void *stream, const uint8_t *cand_dev, const uint8_t *t
 int stcn_masks_resize_nearest(void *stream, const uint8_t *src, int T, int H, int W, const int32_t *frames_dev, int n, int out_h, int out_w,
                               int channels, float *out);
 
+/* ---- frames as stored images (datasets/helpers.py:4-17, generate_annotation_dataset.py:170-174) -------------------------------------
+ * clip_dev fp32 [T,3,H,W] on the device (normalised frames) -> out_dev uint8 [n,H,W,3]: per frame the minimum and the maximum over all
+ * 3 * H * W values, then (x - min) / max(max - min, 1e-8f) * 255, every operation a correctly rounded fp32 one (no contraction, no fast
+ * division), truncated to a byte: what `(im_normalize(tens2image(frame)) * 255).astype(uint8)` gives on the host, byte for byte.
+ * INPUTS ARE FINITE: with a NaN or an infinity in a frame its image is unspecified.  frames_dev: int32 [n] on the device, the frames to take,
+ * in that order (repeats allowed), or NULL = frames 0 .. n - 1.  A frame index outside [0,T) reads nothing and gives an image of zeros.
+ * scratch_dev: n * 2 * 4 bytes, 4-byte aligned; the call initialises it on `stream`.  Three launches on `stream`, no sync.
+ * Null clip_dev / scratch_dev / out_dev, n < 0, n > 65535, T, H or W below 1, H * W above 2^24 and a clip_dev or scratch_dev that is not
+ * 4-byte aligned return STCN_E_INVALID with a message before any device call; n == 0 is a successful no-op. */
+int stcn_frames_to_rgb8(void *stream, const float *clip_dev, int T, int H, int W, const int32_t *frames_dev, int n, void *scratch_dev,
+                        uint8_t *out_dev);
+
 #ifdef __cplusplus
 }
 #endif
