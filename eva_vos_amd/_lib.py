@@ -116,6 +116,8 @@ PROTOTYPES = {
     "stcn_robot_best_mask": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "stcn_masks_resize_nearest": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P]),
     "stcn_frames_to_rgb8": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "stcn_prob_upsample_argmax": (_I, [_P, _P] + [_I] * 12 + [_P]),
+    "stcn_frames_downsample_aa": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "stcn_bench_conv": (_I, [_P] + [_I] * 11 + [C.POINTER(_F), C.POINTER(_D)]),
     "stcn_bench_mfma_rate": (_I, [_P, _I, C.POINTER(_F), C.POINTER(_F)]),
     "stcn_pool_release": (_I, []),

@@ -676,6 +676,37 @@ int stcn_frames_to_rgb8(void *stream, const float *clip_dev, int T, int H, int W
     return STCN_OK;
 }
 
+// ---- a clip at a working resolution (rescale.hip): every argument is checked before any device call -------------------------------------
+int stcn_prob_upsample_argmax(void *stream, const float *prob, int k1, int T, int nh, int nw, int lh, int lw, int h, int w, int H, int W, int t0, int t1,
+                              uint8_t *masks_out) {
+    const char *who = "stcn_prob_upsample_argmax";
+    if (!prob || !masks_out) { set_error("%s: null pointer (%s)", who, !prob ? "prob" : "masks_out"); return STCN_E_INVALID; }
+    if (k1 < 2 || k1 > STCN_MAX_OBJECTS + 1) { set_error("%s: k1 = %d channels outside 2..%d (background + 1..%d objects)", who, k1, STCN_MAX_OBJECTS + 1, STCN_MAX_OBJECTS); return STCN_E_INVALID; }
+    if (T < 1 || nh < 1 || nw < 1) { set_error("%s: bad prob [%d, T = %d, 1, nh = %d, nw = %d]: every size is at least 1", who, k1, T, nh, nw); return STCN_E_INVALID; }
+    if (h < 1 || w < 1 || lh < 0 || lw < 0 || (long)lh + h > nh || (long)lw + w > nw) {
+        set_error("%s: the window h = %d x w = %d at lh = %d, lw = %d is empty or outside the padded plane nh = %d x nw = %d", who, h, w, lh, lw, nh, nw);
+        return STCN_E_INVALID;
+    }
+    if (H < 1 || W < 1 || (long)H * W > MAX_FRAME_PIXELS) { set_error("%s: bad output [T, H = %d, W = %d]: every size is at least 1, H * W at most 2^24", who, H, W); return STCN_E_INVALID; }
+    if (t0 < 0 || t1 > T || t0 > t1) { set_error("%s: frames [t0 = %d, t1 = %d) are no range inside [0, T = %d]", who, t0, t1, T); return STCN_E_INVALID; }
+    if (t0 == t1) return STCN_OK;
+    prob_upsample_argmax_launch(prob, k1, T, nh, nw, lh, lw, h, w, H, W, t0, t1, masks_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
+int stcn_frames_downsample_aa(void *stream, const float *src, int planes, int H, int W, int h, int w, float *dst) {
+    const char *who = "stcn_frames_downsample_aa";
+    if (!src || !dst) { set_error("%s: null pointer (%s)", who, !src ? "src" : "dst"); return STCN_E_INVALID; }
+    if (planes < 1) { set_error("%s: planes = %d, at least 1", who, planes); return STCN_E_INVALID; }
+    if (H < 1 || W < 1 || (long)H * W > MAX_FRAME_PIXELS) { set_error("%s: bad source [planes, H = %d, W = %d]: every size is at least 1, H * W at most 2^24", who, H, W); return STCN_E_INVALID; }
+    if (h < 1 || w < 1) { set_error("%s: bad output [planes, h = %d, w = %d]: every size is at least 1", who, h, w); return STCN_E_INVALID; }
+    if (h > H || w > W) { set_error("%s: h = %d > H = %d or w = %d > W = %d: frames are never enlarged", who, h, H, w, W); return STCN_E_INVALID; }
+    HIPCHK(frames_downsample_aa_launch(src, planes, H, W, h, w, dst, (hipStream_t)stream));
+    HIPCHK(hipGetLastError());
+    return STCN_OK;
+}
+
 int stcn_bench_mfma_rate(void *stream, int ms_target, float *tflops, float *ms_out) {
     if (!tflops || ms_target < 1 || ms_target > 2000) { set_error("stcn_bench_mfma_rate: bad arguments"); return STCN_E_INVALID; }
     hipStream_t s = (hipStream_t)stream;

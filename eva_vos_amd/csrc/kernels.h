@@ -344,6 +344,18 @@ void masks_resize_nearest_launch(const uint8_t *src, int T, int H, int W, const 
 // Enqueues three launches.
 void frames_to_rgb8_launch(const float *clip, int T, int H, int W, const int *frames, int n, void *scratch, uint8_t *out, hipStream_t s);
 
+// ---------------------------------------------------------------- a clip at a working resolution (rescale.hip)
+// prob fp32 [k1,T,1,nh,nw] -> out uint8 [T,H,W], frames [t0,t1) only: the h x w window at (lh, lw) of every channel, bilinear
+// (align_corners=False, torch's fp32 evaluation) to H x W, arg-max over the channels with the lowest index winning a tie.  Nothing outside the
+// window is read, no other frame is written; out may start at any byte.  2 <= k1, the window inside the plane, H * W <= MAX_FRAME_PIXELS
+// (checked by the caller).  Enqueues one launch per 65535 frames.
+void prob_upsample_argmax_launch(const float *prob, int k1, int T, int nh, int nw, int lh, int lw, int h, int w, int H, int W, int t0, int t1,
+                                 uint8_t *out, hipStream_t s);
+// src fp32 [planes,H,W] -> dst fp32 [planes,h,w], h <= H, w <= W: antialiased bicubic (A = -0.5, align_corners=False), horizontal then vertical,
+// fp64 sums rounded once.  The taps of (H -> h) and (W -> w) are built on the host and uploaded on first use, per device (a blocking copy, then
+// cached for the life of the process): the error of that upload comes back.  Enqueues one launch per 65535 planes.
+hipError_t frames_downsample_aa_launch(const float *src, int planes, int H, int W, int h, int w, float *dst, hipStream_t s);
+
 // ---------------------------------------------------------------- frame distances (frame_select.hip)
 // dist [T][T] fp64 = squared L2 distances between T vectors of K fp32 values, vector t at x + index.v[t] * stride (16-byte aligned: x and
 // stride multiples of 4 floats, K % 4 == 0, K >= 4, 1 <= T <= FRAME_GRAM_MAX_T).  The Gram matrix is accumulated in fp64 on the matrix cores

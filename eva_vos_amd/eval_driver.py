@@ -33,6 +33,7 @@ from __future__ import annotations
 import argparse
 import copy
 import csv
+import functools
 import os
 import random
 import threading
@@ -49,6 +50,7 @@ from . import metrics
 from .frame_select import farthest_frame
 from .fq_driver import ClipDataset, add_stats, gather_sorted, lane_cores, load_networks, rank_samples, report_and_leave, run_lanes
 from .sessions import MASK_SECONDS, NO_OBJECT, SKIP_SECONDS, SessionPolicy, annotation_session, frame_quality, session_result
+from .working_size import ScaledInferenceCore, check_working_size
 
 ANNOTATORS = ("component",)                                   # built in; a real SAM controller is passed through run(..., annotator=...)
 MAX_OBJECTS = 32                                              # STCN_MAX_OBJECTS
@@ -404,7 +406,7 @@ def _session_rows(res: dict, i: int, sample, multi_object: bool):
 
 def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "oracle_mask", rounds: int = 60,
         metric: str = "j_and_f", qnet=None, seed: int = 0, device: str = "cuda", lanes: int = 2, stats: dict = None,
-        multi_object: bool = False, share_frames: bool = True, annotator=None, annotation_types=None, agent=None):
+        multi_object: bool = False, share_frames: bool = True, annotator=None, annotation_types=None, agent=None, working_size=None):
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
     (rows: sample id, round, mu_metric, annotation_time, annotated frame, T, then T per-frame values, NaN-padded).
     `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited), `interactions`, `key_frames_encoded` (frames that
@@ -425,8 +427,11 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     `multi_object`: one session per VIDEO with all its objects in one engine.  The rows keep their schema and the sample ids of the per-object
     enumeration, one per (video, object, round), so the outputs of the two modes join on (sample id, round): mu_metric = the mean of that
     object's quality over the frames where it is present, annotation_time = 80 s if the object is present in the annotated frame, else
-    3 s, the annotated frame is the session's, the per-frame values are that object's."""
+    3 s, the annotated frame is the session's, the per-frame values are that object's.
+    `working_size` (an int; None: the clip's own size, as before): the engines propagate on the clip brought down to that shorter side and
+    the masks every round is scored on come back at the clip's own size (working_size.ScaledInferenceCore takes InferenceCore's place)."""
     from mivos.inference_core import InferenceCore
+    core_class = InferenceCore if check_working_size(working_size) is None else functools.partial(ScaledInferenceCore, working_size=working_size)
     spec = POLICY_TABLE[policy]
     if multi_object and not spec.multi_object:
         raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
@@ -443,7 +448,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     _check_l2_clip(policy, t_max, "the longest clip")
     share_frames = share_frames and not multi_object
     rank, mine = rank_samples(ds, share_frames, multi_object)
-    cores = lane_cores(InferenceCore, prop_net, fuse_net, lanes, share_frames, multi_object)
+    cores = lane_cores(core_class, prop_net, fuse_net, lanes, share_frames, multi_object)
     width = 6 + t_max + len(spec.tail)
     job = SimpleNamespace(policy=policy, rounds=rounds, metric=metric, qnet=qnet, agent=agent, annotation_types=annotation_types, seed=seed,
                           multi_object=multi_object, share_frames=share_frames, lane=threading.local())
@@ -512,7 +517,11 @@ def main():
     ap.add_argument("--top-k", type=int, default=50, help="rows of the memory bank each query reads, 1..50 (PropagationNetwork(top_k=...): 20 for STCN checkpoints, 50 for MiVOS)")
     ap.add_argument("--km", type=float, default=None, metavar="SIGMA", help="kernelized memory read: standard deviation (1/16-scale positions) of the Gaussian "
                     "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
+    ap.add_argument("--working-size", type=int, default=None, metavar="N", help="propagate on the clip resized so that its shorter side is N (antialiased bicubic, "
+                    "e.g. 480; clips that are no larger keep their size) and score the masks brought back to the clip's own size; default: the clip's own size")
     a = ap.parse_args()
+    if a.working_size is not None and a.working_size < 1:
+        ap.error(f"--working-size {a.working_size}: the length of the shorter side, at least 1")
     spec = POLICY_TABLE[a.policy]
     typed = "annotation_types" in spec.needs
     if a.annotation_types and "agent" in spec.needs:
@@ -534,7 +543,8 @@ def main():
         agent = (PPOAgent(state_dict=synth.recipe_state_dict(ActorCritic(), seed=5)) if a.synthetic_weights else PPOAgent(model_path=a.agent_weights))
     out = os.path.join("Experiments", a.db, "_".join([a.policy] + (sorted(a.annotation_types) if typed else [])) + ".csv")
     rows = run(a.root, a.imset, out, prop, fuse, a.policy, a.rounds, qnet=qnet, lanes=a.lanes, multi_object=a.multi_object,
-               share_frames=not a.no_share_frames, annotator=a.annotator if "annotator" in spec.needs else None, annotation_types=a.annotation_types, agent=agent)
+               share_frames=not a.no_share_frames, annotator=a.annotator if "annotator" in spec.needs else None, annotation_types=a.annotation_types, agent=agent,
+               working_size=a.working_size)
     report_and_leave(f"{len(rows)} rounds -> {out}")
 
 

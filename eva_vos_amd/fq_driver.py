@@ -544,20 +544,27 @@ def save_rgb_frames(rgb: torch.Tensor, out_dir: str, pool=None):
 
 
 def run(root: str, imset: str, out: str, prop_net, fuse_net, rounds: int = 8, save_masks: bool = True,
-        device: str = "cuda", lanes: int = 2, stats: dict = None, share_frames: bool = True):
+        device: str = "cuda", lanes: int = 2, stats: dict = None, share_frames: bool = True, working_size=None):
     """Process this rank's share of the samples (`lanes` videos in flight); returns the gathered rows on every rank
     (rows: sample id, round, selected frame, T, then T per-frame J values padded with NaN).
     `stats` (optional dict): this rank's `propagated_frames` (frames the engines visited), `interactions`, `key_frames_encoded` (frames
     that went through the key encoder) and `engines_created` are added to it.
     `share_frames`: the sessions of a video's objects run one after the other on ONE engine that keeps the clip and its frame features
     between them (LaneCores) - videos, not samples, are dealt to ranks and lanes.  Same rows, same files; False: a fresh engine and a
-    fresh upload per sample, samples dealt one by one."""
+    fresh upload per sample, samples dealt one by one.
+    `working_size` (an int; None: the clip's own size, as before): the engines propagate on the clip brought down to that shorter side, J is
+    computed on the masks brought back to the clip's own size (working_size.ScaledInferenceCore takes InferenceCore's place); the 224 x 224
+    frames and states are made from own-size data as before."""
+    import functools
     from concurrent.futures import ThreadPoolExecutor
 
     from mivos.inference_core import InferenceCore
+
+    from .working_size import ScaledInferenceCore, check_working_size
+    core_class = InferenceCore if check_working_size(working_size) is None else functools.partial(ScaledInferenceCore, working_size=working_size)
     ds = ClipDataset(root, imset)
     rank, mine = rank_samples(ds, share_frames)
-    cores = lane_cores(InferenceCore, prop_net, fuse_net, lanes, share_frames)
+    cores = lane_cores(core_class, prop_net, fuse_net, lanes, share_frames)
     width = 4 + max(s[2] for s in ds.samples)
     writers = ThreadPoolExecutor(8) if save_masks else None           # zlib releases the GIL: the encoders really run beside the lanes
     pending = []
@@ -654,9 +661,13 @@ def main():
     ap.add_argument("--top-k", type=int, default=50, help="rows of the memory bank each query reads, 1..50 (PropagationNetwork(top_k=...): 20 for STCN checkpoints, 50 for MiVOS)")
     ap.add_argument("--km", type=float, default=None, metavar="SIGMA", help="kernelized memory read: standard deviation (1/16-scale positions) of the Gaussian "
                     "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
+    ap.add_argument("--working-size", type=int, default=None, metavar="N", help="propagate on the clip resized so that its shorter side is N (antialiased bicubic, "
+                    "e.g. 480; clips that are no larger keep their size) and score the masks brought back to the clip's own size; default: the clip's own size")
     a = ap.parse_args()
+    if a.working_size is not None and a.working_size < 1:
+        ap.error(f"--working-size {a.working_size}: the length of the shorter side, at least 1")
     prop, fuse = load_networks(a)
-    rows = run(a.root, a.imset, a.out, prop, fuse, a.rounds, lanes=a.lanes, share_frames=not a.no_share_frames)
+    rows = run(a.root, a.imset, a.out, prop, fuse, a.rounds, lanes=a.lanes, share_frames=not a.no_share_frames, working_size=a.working_size)
     report_and_leave(f"{len(rows)} states -> {os.path.join(a.out, 'res_' + os.path.splitext(os.path.basename(a.imset))[0] + '.csv')}")
 
 

@@ -662,6 +662,26 @@ int stcn_masks_resize_nearest(void *stream, const uint8_t *src, int T, int H, in
 int stcn_frames_to_rgb8(void *stream, const float *clip_dev, int T, int H, int W, const int32_t *frames_dev, int n, void *scratch_dev,
                         uint8_t *out_dev);
 
+/* ---- a clip at a working resolution: frames down before the engine, masks up after it --------------------------------------------------
+ * stcn_prob_upsample_argmax: prob fp32 [k1,T,1,nh,nw] on the device (an engine's padded probabilities, k1 = objects + 1) -> masks_out uint8
+ * [T,H,W].  For every frame t in [t0,t1) the unpadded window of h x w values at row lh, column lw of each channel is interpolated bilinearly
+ * to H x W - align_corners=False: src = (dst + 0.5) * in / out - 0.5, clamped below at 0, i1 = min(i0 + 1, in - 1), evaluated in fp32 - and
+ * the arg-max over the channels is written as one byte; the lowest index wins a tie.  The interpolated probabilities are never stored.  The
+ * padded rows and columns of prob are not read (edges clamp at the window); frames outside [t0,t1) are not written; masks_out may start at
+ * any byte.  One launch on `stream` (per 65535 frames), no sync; t0 == t1 is a successful no-op.
+ * Null prob / masks_out, k1 outside 2..STCN_MAX_OBJECTS + 1, a size below 1, a window outside the padded plane (lh + h > nh, lw + w > nw, a
+ * negative lh or lw), H * W above 2^24 and t0 > t1 or a range outside [0,T] return STCN_E_INVALID with a message before any device call. */
+int stcn_prob_upsample_argmax(void *stream, const float *prob, int k1, int T, int nh, int nw, int lh, int lw, int h, int w, int H, int W,
+                              int t0, int t1, uint8_t *masks_out);
+/* stcn_frames_downsample_aa: src fp32 [planes,H,W] on the device -> dst fp32 [planes,h,w], h <= H and w <= W: antialiased bicubic resampling
+ * (A = -0.5, align_corners=False: what F.interpolate(mode="bicubic", antialias=True) defines), a horizontal and a vertical pass with fp64
+ * products and sums, rounded to fp32 once.  Per axis the support is 2 * in / out source pixels to either side of the output's centre and the
+ * weights are normalised over the part of it inside the image; the tables of an (in, out) pair are built on the host and uploaded at the
+ * first call that needs them (a blocking copy; kept per device for the life of the process), every later call only enqueues: one launch on
+ * `stream` (per 65535 planes), no sync.  Null src / dst, a size below 1, H * W above 2^24 and h > H or w > W (frames are never enlarged)
+ * return STCN_E_INVALID with a message before any device call. */
+int stcn_frames_downsample_aa(void *stream, const float *src, int planes, int H, int W, int h, int w, float *dst);
+
 #ifdef __cplusplus
 }
 #endif
