@@ -96,6 +96,19 @@ private:
 };
 
 size_t wino_v_capacity(const Dims &d, int maxb);     // Work::wino_v_floats of a workspace whose largest conv batch is maxb
+// What the V workspace holds: set by run_conv after the input transform of an unchunked F(4x4) launch, cleared by every other launch that
+// writes the workspace (F(2x2), a chunked F(4x4) launch).  It names the tensor as the transform read it - not its contents: only a conv
+// whose caller states that the tensor has not been written since (ConvArgs::reuse_v) compares it.
+struct VToken {
+    const float *x = nullptr;           // null: nothing to reuse
+    long bs = 0; unsigned bytes = 0;    // batch stride, extent of the descriptor
+    int B = 0, H = 0, W = 0, C = 0;
+    int relu = 0;                       // ReLU on the input AS IT TAKES EFFECT (0 for a tensor stated non-negative)
+    int Mt_pad = 0;                     // padded tile count: with B, H, W the layout of V
+    bool operator==(const VToken &o) const {
+        return x == o.x && bs == o.bs && bytes == o.bytes && B == o.B && H == o.H && W == o.W && C == o.C && relu == o.relu && Mt_pad == o.Mt_pad;
+    }
+};
 // scratch for one in-flight frame computation (sized for nh x nw and k objects)
 struct Work {
     Dims d{};
@@ -104,6 +117,7 @@ struct Work {
     float *A = nullptr, *B = nullptr, *C = nullptr, *D = nullptr;
     float *splitk = nullptr; size_t splitk_floats = 0;
     float *wino_v = nullptr; size_t wino_v_floats = 0;   // Winograd-transformed input of the conv in flight
+    VToken v_token;                     // what wino_v holds after the last launch through this workspace
     float *cbam = nullptr;
     float *readout = nullptr;           // [k][hw16][512]
     float *logit4 = nullptr;            // [k][hw4]
@@ -144,6 +158,11 @@ struct ConvArgs {
     float *y = nullptr; long y_bs = 0;
     const float *res = nullptr; long res_bs = CONV_DENSE; int res_bmod = 0;   // res_bmod: see ConvP
     int relu_in = 0, relu_out = 0, force_splitk = 0;
+    int x_nonneg = 0;       // the caller states: no input value is negative (relu_in has no effect on it)
+    int reuse_v = 0;        // the caller states: the previous conv of this workspace read this very tensor and nothing wrote it since -
+                            // when Work::v_token agrees, the launch takes V from the workspace instead of transforming again
+    ConvArgs &nonneg_input() { x_nonneg = 1; return *this; }
+    ConvArgs &same_input_as_last(bool yes = true) { reuse_v = yes; return *this; }
     ConvArgs(const float *x, int c, int B_, int H_, int W_, long bs = CONV_DENSE) : x0(x), c0(c), bs0(bs), B(B_), H(H_), W(W_) {}
     ConvArgs &concat(const float *x, int c, long bs) { x1 = x; c1 = c; bs1 = bs; return *this; }
     ConvArgs &strided(int s) { stride = s; return *this; }

@@ -58,6 +58,9 @@ struct Knobs {
     int fusion_wino = 1;        // STCN_FUSION_WINO: FusionNet convs as Winograd F(2x2) inside the workgroup
     int pw_chain = 2;           // STCN_PW_CHAIN: large pointwise convs on the chain kernel (several tiles per workgroup, one pipeline): 0 off,
                                 // 1 consecutive tiles per workgroup, 2 tiles strided over the grid (default)
+    // how the 32-tile F(4x4) GEMM is fed (neither changes a bit of any output):
+    int wino4_piece_xcd = 1;    // STCN_WINO4_PIECE_XCD: K-piece workgroups in 2-D blocks per XCD (0: tile-major order, pieces inside)
+    int wino4_share_v = 1;     // STCN_WINO4_SHARE_V: a conv that says so reuses V of the previous transform of the same input (0: always transforms)
     static Knobs from_env();
 };
 
@@ -124,7 +127,7 @@ struct ConvPlan {
     const char *variant = "";       // CONV_DIRECT: conv_variant_name() (the tile plan itself is in ConvP: the kernels read it)
     bool tail = false;              // CONV_DIRECT: tail balancing (p.rem_split > 1)
     size_t v_floats = 0;            // Winograd families: V workspace floats
-    int n_in = 0, n_gemm = 1;       // input-transform / GEMM launches (the chunks of an F(4x4) launch)
+    int n_in = 0, n_gemm = 1;       // input-transform / GEMM launches (the chunks of an F(4x4) launch; n_in = 0 when run_conv found V in the workspace)
     bool reduce = false;            // a reduce launch follows
     double fl = 0;                  // algorithmic FLOP (set before the family plans)
     double fl_exec = 0;             // FLOP the matrix cores execute (Winograd: fewer)

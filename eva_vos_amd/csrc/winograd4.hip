@@ -156,9 +156,14 @@ struct Wino4G {
     // 2-D blocks per XCD (whole-tile workgroups): an XCD's contiguous range of xb_m x xb_n workgroups covers xb_m tile blocks x xb_n
     // channel blocks instead of a strip of rows - xb_m + xb_n operand streams through its L2 instead of rows + tiles_n (0: strips)
     int xb_m, xb_n, xb_cols;
+    // the same for the K-piece workgroups (whole rows of tiles from row full_wg / tiles_n on): an XCD's contiguous range is pb_m tile blocks
+    // x pb_n channel blocks with ALL their pieces, so it streams pb_m / rows of V and pb_n / tiles_n of U once (0: tile-major order, pieces inside)
+    int pb_m, pb_n, pb_cols;
 };
 
-// MB = 32-tile blocks per workgroup.  MB = 1: three fragment sets, loads two k-blocks ahead.  MB = 2 (64 tiles x 32 channels: 25 %
+// MB = 32-tile blocks per workgroup.  MB = 1: three fragment sets, loads two k-blocks ahead.  (A fourth set, three k-blocks ahead, fits - 148
+// registers, no scratch, still three waves per SIMD - and was measured SLOWER: 55.5 against 54.0 ms of this kernel in the solo trace, three
+// runs each, profiles/wino4_feed.txt.  Not kept.)  MB = 2 (64 tiles x 32 channels: 25 %
 // fewer L2 bytes per MFMA, half the U traffic): 96 accumulator registers leave room for two HALF fragment sets - the loop walks
 // half-steps (k-block, 32-tile block) and loads one half-step ahead (12 MFMAs x 3 waves sharing the SIMD: ~2300 cycles).
 template <int MB>
@@ -168,9 +173,17 @@ __global__ __launch_bounds__(64 * W4W) void wino4_gemm_kernel(const Wino4G p, co
     int swz, piece = -1, kb0 = 0, kb1 = p.KB;
     if (MB == 1 && p.pieces > 1 && (int)blockIdx.x >= p.full_wg) {           // a K piece of one of the last tiles
         const int j = xcd_contiguous_block((int)blockIdx.x - p.full_wg, (int)gridDim.x - p.full_wg);
-        const int rt = j / p.pieces;
-        piece = j - rt * p.pieces;
-        swz = p.full_wg + rt;
+        if (p.pb_n > 0) {                                                     // j = block * (pieces pb_m pb_n) + (piece, row, column) inside the block
+            const int cell = p.pb_m * p.pb_n, per = cell * p.pieces, blk = j / per, in = j - blk * per;
+            const int bm_i = blk / p.pb_cols, bn_i = blk - bm_i * p.pb_cols;
+            piece = in / cell;
+            const int rc = in - piece * cell, im = rc / p.pb_n;
+            swz = p.full_wg + (bm_i * p.pb_m + im) * tiles_n + bn_i * p.pb_n + (rc - im * p.pb_n);
+        } else {
+            const int rt = j / p.pieces;
+            piece = j - rt * p.pieces;
+            swz = p.full_wg + rt;
+        }
         kb0 = piece * p.kb_per_piece;
         kb1 = min(p.KB, kb0 + p.kb_per_piece);
     } else {
@@ -592,14 +605,36 @@ void wino4_launch(const ConvP &p, const ConvPlan &cp, float *V, hipStream_t s, h
             if (best && best != tiles_n) { g.xb_n = best; g.xb_m = per / best; g.xb_cols = tiles_n / best; }
         }
     }
+    g.pb_m = g.pb_n = g.pb_cols = 0;
+    if (p.kn.wino4_piece_xcd && pl.pieces > 1 && pl.full_wg % tiles_n == 0) {
+        // The same search for the K-piece workgroups (the tail of a launch, or all of a small one): rows x tiles_n tiles, each in `pieces`
+        // pieces.  Tile-major with the pieces inside, an XCD's eighth is one or two tile blocks with MANY channel blocks: the 1024 -> 512
+        // frame parts of the value encoder (4 x 16 tiles, 4 pieces) streamed half of U through every L2.  8 equal blocks of bm tile blocks
+        // x bn channel blocks with all their pieces; fewest operand streams, the narrower block in channels on a tie.  Nothing divides:
+        // the order stays as it was.  Only WHICH workgroup computes a (tile, piece) changes - the slabs and the reduce do not.
+        const int rows = tiles_m - pl.full_wg / tiles_n, cells = rows * tiles_n;
+        if (cells % 8 == 0) {
+            const int per = cells / 8;
+            int best = 0, best_sum = 0;
+            for (int bn = 1; bn <= tiles_n; ++bn) {
+                if (per % bn || tiles_n % bn) continue;
+                const int bm = per / bn;
+                if (rows % bm || (rows / bm) * (tiles_n / bn) != 8) continue;
+                if (!best || bm + bn < best_sum) { best_sum = bm + bn; best = bn; }
+            }
+            if (best) { g.pb_n = best; g.pb_m = per / best; g.pb_cols = tiles_n / best; }
+        }
+    }
     const size_t lds = (size_t)36 * W4T * W4N * sizeof(float);
     for (int c = 0; c < pl.chunks; ++c) {
         const int tm_lo = c * pl.tm_per_chunk, tm_hi = tm_lo + pl.tm_per_chunk < tiles_m ? tm_lo + pl.tm_per_chunk : tiles_m;
         const int tile_lo = tm_lo * W4T * mb, tile_hi = pl.chunks == 1 ? ge.Mt_pad : tm_hi * W4T * mb;
         hipEvent_t *ei = ev_in ? ev_in[c] : nullptr, *eg = ev_gemm ? ev_gemm[c] : nullptr;
-        const WinoInGrid ig = wino_input_grid(tile_hi - tile_lo, p.Cin);
-        launch(wino4_input_kernel, dim3(ig.gx, ig.chunks), dim3(256), 0, s, ei, p.x0, p.x0_bytes, p.bs0, p.H, p.W, p.Cin, p.relu_in, ge.TH, ge.TW,
-               ge.Mt, ge.Mt_pad, ig.per, tile_lo, tile_hi, V);
+        if (cp.n_in) {                                                        // 0: the workspace holds V of this input already (run_conv's token)
+            const WinoInGrid ig = wino_input_grid(tile_hi - tile_lo, p.Cin);
+            launch(wino4_input_kernel, dim3(ig.gx, ig.chunks), dim3(256), 0, s, ei, p.x0, p.x0_bytes, p.bs0, p.H, p.W, p.Cin, p.relu_in, ge.TH, ge.TW,
+                   ge.Mt, ge.Mt_pad, ig.per, tile_lo, tile_hi, V);
+        }
         g.tm0 = tm_lo;
         if (mb == 2) {
             const int grid = (tm_hi - tm_lo) * tiles_n;
