@@ -24,6 +24,10 @@ Differences by design:
 * ``--multi-object`` (an additional mode; the reference's per-object protocol stays the default): ONE session per video with all its
   objects in one engine - the key encoder runs once per frame, not once per frame and object - scored per round by the k-object
   evaluation on the device (``stcn_metrics_objects_round``); rows stay one per (video, object, round) with the per-object sample ids.
+* the dataset-level video ranking of the paper (Eq. 3; ``vis/vis_util.py:40-150``) is ``eva_vos_amd/ranking.py``: ``--rank`` writes the
+  reference-schema CSV and the ranking beside the experiment CSV after a full run; ``--budget-hours`` / ``--target-metric`` apply it WHILE
+  the sessions run (``eva_vos_amd/budget.py``: every video's session is suspended between its rounds, the rounds the ranking never reaches
+  are not run).
 
 Usage:  python -m eva_vos_amd.eval_driver --root data/MOSE --imset data/MOSE/ImageSets/test.txt --policy oracle_mask
         (multi-GPU: python -m torch.distributed.run --nproc-per-node N -m eva_vos_amd.eval_driver ...)
@@ -49,7 +53,7 @@ import torch
 from . import metrics
 from .frame_select import farthest_frame
 from .fq_driver import ClipDataset, add_stats, gather_sorted, lane_cores, load_networks, rank_samples, report_and_leave, run_lanes
-from .sessions import MASK_SECONDS, NO_OBJECT, SKIP_SECONDS, SessionPolicy, annotation_session, frame_quality, session_result
+from .sessions import MASK_SECONDS, NO_OBJECT, SKIP_SECONDS, SessionPolicy, SteppedSession, annotation_rounds, frame_quality, session_result
 from .working_size import ScaledInferenceCore, check_working_size
 
 ANNOTATORS = ("component",)                                   # built in; a real SAM controller is passed through run(..., annotator=...)
@@ -108,7 +112,7 @@ def _upper_bound_frame_in_place(processor, scorer, gt, frames, stats=None):
 
 
 def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and_f", qnet=None, rng=None, multi_object: bool = False,
-               stats: dict = None):
+               stats: dict = None, steps: bool = False):
     """One sample through ``rounds`` annotation rounds.  Returns dict(mu_metrics, annotation_times, frames,
     round_metrics, propagated_frames): mu_metrics[r] / annotation_times[r] as the reference returns them; frames = annotated frames in
     order; round_metrics[r] = per-frame quality after round r; propagated_frames = frames the engine really visited (rounds >= 2 only
@@ -123,7 +127,10 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
     ``stats`` (optional dict): ``propagated_frames`` and ``interactions`` of the session's own rounds are added to it, and for the upper
     bound ``trial_interactions`` (candidates tried) and ``engine_clones`` (deep copies made).
     ``l2_mask`` chooses ``farthest_frame(processor.frame_distances(), frames)``; a clip longer than the key cache raises ValueError before the
-    processor is touched; ``stats["frame_distance_passes"]`` counts the engine passes the session added (0 when the core came with the matrix)."""
+    processor is touched; ``stats["frame_distance_passes"]`` counts the engine passes the session added (0 when the core came with the matrix).
+    ``steps=True``: nothing is run; the suspended session comes back (a ``sessions.SteppedSession``: ``step()`` one round, ``result()`` the
+    values above as of the rounds run, ``close()`` at the end) - the engines have no state across sessions and the draws are the session's own,
+    so a session stepped between other videos' rounds gives the bytes it gives run straight through."""
     assert policy in POLICIES, policy
     if multi_object and policy not in MULTI_OBJECT_POLICIES:
         raise ValueError(f"multi-object sessions support the policies {' and '.join(MULTI_OBJECT_POLICIES)}, not {policy}")
@@ -169,18 +176,22 @@ def run_policy(policy: str, processor, sample, rounds: int, metric: str = "j_and
     if in_place:
         processor.set_undo_depth(max(depth, 1))
     passes = processor.frame_distance_passes if policy == "l2_mask" else 0
-    try:
-        ses = annotation_session(processor, scorer, T, rounds, session, stats)
-    finally:
+
+    def close():
         if in_place:
             processor.set_undo_depth(depth)                        # the core goes back to its lane as it came
-    if policy == "l2_mask":
-        stats["frame_distance_passes"] = stats.get("frame_distance_passes", 0) + processor.frame_distance_passes - passes
-    res = dict(session_result(scorer, ses), frames=ses["chosen"])
-    if multi_object:
-        oq = scorer.object_qualities()
-        res.update(object_metrics=[oq[i].copy() for i in range(len(ses["costs"]))], present=scorer.present_host)
-    return res
+        if policy == "l2_mask":
+            stats["frame_distance_passes"] = stats.get("frame_distance_passes", 0) + processor.frame_distance_passes - passes
+
+    def result(ses):
+        res = dict(session_result(scorer, ses), frames=ses["chosen"])
+        if multi_object:
+            oq = scorer.object_qualities()
+            res.update(object_metrics=[oq[i].copy() for i in range(len(ses["costs"]))], present=scorer.present_host)
+        return res
+
+    stepped = SteppedSession(annotation_rounds(processor, scorer, T, rounds, session, stats), result, close)
+    return stepped if steps else stepped.run()
 
 
 def oracle_action(annotator, annotation_types, gt_mask, mivos_mask, im, frame_annots, empty=None):
@@ -216,7 +227,7 @@ def _one_object_session(policy: str, processor, sample, rounds: int, metric: str
 
 
 def run_typed_policy(policy: str, processor, sample, rounds: int, annotator, annotation_types, metric: str = "j_and_f", rng=None,
-                     stats: dict = None, scorer=None, choose_action=None):
+                     stats: dict = None, scorer=None, choose_action=None, steps: bool = False):
     """One sample through ``rounds`` rounds of a mixed-annotation policy (``rand_type``, ``rand_rand``, ``oracle_oracle``:
     interactions/mulitple_annotations.py:161-220, 223-283, 104-158).  ``annotator``: an ``annotate.PromptAnnotator``; ``annotation_types``:
     'click', 'bbox', 'mask' or '<N>clicks' - exactly one for ``rand_type``, more than one for the others.  The first round is the mask of frame
@@ -227,7 +238,7 @@ def run_typed_policy(policy: str, processor, sample, rounds: int, annotator, ann
     the policy's action (the hook an ``eva_vos`` agent needs); ``scorer``: another evaluation with ``TypedRoundScorer``'s interface
     (``metrics.HostTypedScorer``).  Returns the reference's values - ``mu_metrics``, ``annotation_times``, ``annotations_actions``, and
     ``round_metrics`` / ``annotated_frames`` (the reference returns these two for ``oracle_oracle`` only) - plus ``types`` and
-    ``propagated_frames``."""
+    ``propagated_frames``.  ``steps=True``: the suspended session instead (see ``run_policy``)."""
     from .annotate import check_annotation_types
     assert policy in TYPED_POLICIES, policy
     types_ = check_annotation_types(annotation_types)
@@ -257,13 +268,14 @@ def run_typed_policy(policy: str, processor, sample, rounds: int, annotator, ann
         return int(rng.choice(left.tolist())) if len(left) else None
 
     session = SessionPolicy(lambda f: gt[f][None], choose_frame, action=choose_action or policy_action, stop_at_T=False)
-    ses = annotation_session(processor, scorer, T, rounds, session, {} if stats is None else stats)
-    return dict(session_result(scorer, ses), annotations_actions=ses["actions"], annotated_frames=ses["frames"], frames=ses["frames"], types=ses["types"],
-                action_data=action_data)
+    stepped = SteppedSession(annotation_rounds(processor, scorer, T, rounds, session, {} if stats is None else stats),
+                             lambda ses: dict(session_result(scorer, ses), annotations_actions=ses["actions"], annotated_frames=ses["frames"],
+                                              frames=ses["frames"], types=ses["types"], action_data=action_data))
+    return stepped if steps else stepped.run()
 
 
 def run_eva_vos(processor, sample, rounds: int, annotator, qnet, agent, metric: str = "j_and_f", rng=None, stats: dict = None, scorer=None,
-                selector=None):
+                selector=None, steps: bool = False):
     """One sample through ``rounds`` rounds of ``eva_vos`` (interactions/mulitple_annotations.py:307-378): the first round is the mask of frame
     0 at 80 s; every later round the AGENT chooses how the pending frame is annotated (``rl_agent_annotate``, :286-304) and the QNET which
     frame comes next (:356-369).  ``annotator``: an ``annotate.PromptAnnotator`` whose predictor gives an image embedding; ``qnet``: a
@@ -273,7 +285,7 @@ def run_eva_vos(processor, sample, rounds: int, annotator, qnet, agent, metric: 
     ``sample['rgb']``; its ``masks_to_input`` (``agent.masks_to_224`` by default) also builds the agent's mask input; ``scorer``: another evaluation with ``TypedRoundScorer``'s interface (``metrics.HostTypedScorer``).
     The annotation types are the reference's hard-coded ``['3clicks', 'mask'][action]``, plus 'no_object' (3 s, value 0, no agent call) on a frame
     without the object.  Returns the reference's values - ``mu_metrics``, ``annotation_times``, ``rl_values`` (the first entry is -2, :316),
-    ``annotations_actions``, ``round_metrics``, ``annotated_frames`` - plus ``frames``, ``types`` and ``propagated_frames``."""
+    ``annotations_actions``, ``round_metrics``, ``annotated_frames`` - plus ``frames``, ``types`` and ``propagated_frames``.  ``steps=True``: the suspended session instead (see ``run_policy``)."""
     from .agent import AVAIL_ACTIONS, masks_to_224
     from .annotate import ANNOTATION_COSTS
     T, gt, images, scorer = _one_object_session("eva_vos", processor, sample, rounds, metric, scorer)
@@ -305,9 +317,10 @@ def run_eva_vos(processor, sample, rounds: int, annotator, qnet, agent, metric: 
         return selector.select(gen, left.tolist()) if len(left) else None
 
     session = SessionPolicy(lambda f: gt[f][None], select, action=choose_action, stop_at_T=False)
-    ses = annotation_session(processor, scorer, T, rounds, session, {} if stats is None else stats)
-    return dict(session_result(scorer, ses), rl_values=rl_values, annotations_actions=ses["actions"], annotated_frames=ses["frames"], frames=ses["frames"],
-                types=ses["types"])
+    stepped = SteppedSession(annotation_rounds(processor, scorer, T, rounds, session, {} if stats is None else stats),
+                             lambda ses: dict(session_result(scorer, ses), rl_values=rl_values, annotations_actions=ses["actions"],
+                                              annotated_frames=ses["frames"], frames=ses["frames"], types=ses["types"]))
+    return stepped if steps else stepped.run()
 
 
 def make_annotator(name: str):
@@ -332,7 +345,8 @@ ARGUMENTS = {"qnet": "a QualityNet in eval mode", "agent": "an agent.PPOAgent", 
 @dataclass(frozen=True)
 class PolicySpec:
     """All that run() and main() know of a policy.  ``runner(job, proc, sample, i, session_stats)``: sample i through its session (``job``: the
-    arguments of run() and ``lane``, what the lane thread keeps between its sessions: its annotator, eva_vos's selector); ``needs``: the keys of ARGUMENTS the policy cannot run without; ``multi_object``:
+    arguments of run(), ``lane``, what the lane thread keeps between its sessions: its annotator, eva_vos's selector, and ``steps``, whether
+    the suspended session is wanted instead of its result); ``needs``: the keys of ARGUMENTS the policy cannot run without; ``multi_object``:
     it has a multi-object mode; ``tail``: its extra columns in CSV order, kept at the END of a row, column j at ``row[-1 - j]``;
     ``action_names(annotation_types)``: the names an ACTIONS column indexes; ``seconds``: how the CSV prints ``annotation_time`` - the mask
     policies cost whole seconds, click costs are fractions of one."""
@@ -346,12 +360,12 @@ class PolicySpec:
 
 def _run_mask(job, proc, sample, i, session):
     return run_policy(job.policy, proc, sample, job.rounds, job.metric, job.qnet, random.Random(job.seed * 100003 + i), multi_object=job.multi_object,
-                      stats=session)
+                      stats=session, steps=job.steps)
 
 
 def _run_typed(job, proc, sample, i, session):
     return run_typed_policy(job.policy, proc, sample, job.rounds, job.lane.annotator, job.annotation_types, job.metric,
-                            random.Random(job.seed * 100003 + i), stats=session)
+                            random.Random(job.seed * 100003 + i), stats=session, steps=job.steps)
 
 
 def _run_agent(job, proc, sample, i, session):
@@ -362,7 +376,7 @@ def _run_agent(job, proc, sample, i, session):
             lane.video, lane.selector = sample["video"], QNetSelector(job.qnet, sample["rgb"][0])
         selector = lane.selector
     return run_eva_vos(proc, sample, job.rounds, lane.annotator, job.qnet, job.agent, job.metric, torch.Generator().manual_seed(job.seed * 100003 + i),
-                       stats=session, selector=selector)
+                       stats=session, selector=selector, steps=job.steps)
 
 
 def _typed_action_names(annotation_types):
@@ -402,6 +416,33 @@ def _session_rows(res: dict, i: int, sample, multi_object: bool):
         for r, oq in enumerate(res["object_metrics"]):
             f = res["frames"][r]
             yield sid, r, float(np.mean(oq[o][here])) if here.any() else float("nan"), MASK_SECONDS if here[f] else SKIP_SECONDS, f, oq[o]
+
+
+def result_rows(res: dict, i: int, sample, multi_object: bool, spec: "PolicySpec", action_names, width: int, first_round: int = 0) -> list:
+    """The float32 rows of one session's result, as ``run`` returns them: the common columns, the per-frame values, NaN padding up to
+    ``width``, the policy's tail columns at the end.  ``first_round``: only the rows of that round and later ones."""
+    rows = []
+    for sid, r, mu, sec, f, q in _session_rows(res, i, sample, multi_object):
+        if r < first_round:
+            continue
+        row = np.full(width, np.nan, np.float32)
+        row[:6] = (sid, r, mu, sec, f, len(q))
+        row[6:6 + len(q)] = q
+        for j, col in enumerate(spec.tail):
+            row[-1 - j] = col.fill(res, r, action_names)
+        rows.append(row)
+    return rows
+
+
+def write_rows_csv(out_csv: str, ordered, spec: "PolicySpec", object_names, action_names) -> None:
+    """The experiment CSV of ``run``: ``video, mu_metric, annotation_time, round`` and the policy's tail columns, one line per row."""
+    os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
+    with open(out_csv, "w", newline="") as f:
+        wr = csv.writer(f)
+        wr.writerow(["video", "mu_metric", "annotation_time", "round"] + [col.name for col in spec.tail])
+        for row in ordered:
+            wr.writerow([object_names[int(row[0])], float(row[2]), spec.seconds(row[3]), int(row[1])]
+                        + [col.cell(row[-1 - j], action_names) for j, col in enumerate(spec.tail)])
 
 
 def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "oracle_mask", rounds: int = 60,
@@ -451,7 +492,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     cores = lane_cores(core_class, prop_net, fuse_net, lanes, share_frames, multi_object)
     width = 6 + t_max + len(spec.tail)
     job = SimpleNamespace(policy=policy, rounds=rounds, metric=metric, qnet=qnet, agent=agent, annotation_types=annotation_types, seed=seed,
-                          multi_object=multi_object, share_frames=share_frames, lane=threading.local())
+                          multi_object=multi_object, share_frames=share_frames, lane=threading.local(), steps=False)
 
     def work(i, sample):
         t_c = time.perf_counter()
@@ -465,15 +506,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
         add_stats(stats, dict({n: session[n] for n in ("trial_interactions", "engine_clones", "frame_distance_passes") if n in session},
                               create_s=t_s - t_c, session_s=time.perf_counter() - t_s, propagated_frames=res["propagated_frames"],
                               interactions=len(res["mu_metrics"])))
-        rows = []
-        for sid, r, mu, sec, f, q in _session_rows(res, i, sample, multi_object):
-            row = np.full(width, np.nan, np.float32)
-            row[:6] = (sid, r, mu, sec, f, len(q))
-            row[6:6 + len(q)] = q
-            for j, col in enumerate(spec.tail):
-                row[-1 - j] = col.fill(res, r, action_names)
-            rows.append(row)
-        return rows
+        return result_rows(res, i, sample, multi_object, spec, action_names, width)
 
     def lane_done():
         cores.release()
@@ -483,13 +516,7 @@ def run(root: str, imset: str, out_csv: str, prop_net, fuse_net, policy: str = "
     cores.add_to(stats)
     allrows, ordered = gather_sorted(rows, width)
     if rank == 0 and out_csv:
-        os.makedirs(os.path.dirname(os.path.abspath(out_csv)), exist_ok=True)
-        with open(out_csv, "w", newline="") as f:
-            wr = csv.writer(f)
-            wr.writerow(["video", "mu_metric", "annotation_time", "round"] + [col.name for col in spec.tail])
-            for row in ordered:
-                wr.writerow([ds.object_names[int(row[0])], float(row[2]), spec.seconds(row[3]), int(row[1])]
-                            + [col.cell(row[-1 - j], action_names) for j, col in enumerate(spec.tail)])
+        write_rows_csv(out_csv, ordered, spec, ds.object_names, action_names)
     return allrows
 
 
@@ -519,9 +546,20 @@ def main():
                     "around each memory row's best query (prop_model.memory.km of the reference, e.g. 5.6); default: the plain read")
     ap.add_argument("--working-size", type=int, default=None, metavar="N", help="propagate on the clip resized so that its shorter side is N (antialiased bicubic, "
                     "e.g. 480; clips that are no larger keep their size) and score the masks brought back to the clip's own size; default: the clip's own size")
+    ap.add_argument("--budget-hours", type=float, default=None, metavar="H", help="rank the videos while they run (budget.run_ranked) and stop before the "
+                    "annotation that would pass H annotator hours over the whole imset; one process, per-object sessions, every session resident")
+    ap.add_argument("--target-metric", type=float, default=None, metavar="M", help="the same live ranking, stopped at the first curve point >= M (e.g. 0.85)")
+    ap.add_argument("--gamma", type=float, default=0.6, help="the ranking's discount of the agent's values (eva_vos; the other policies rank by gain)")
+    ap.add_argument("--rank", action="store_true", help="after the full run, write the reference-schema CSV (<policy>_reference.csv) and the ranking "
+                    "(<policy>_ranking.csv: step, video, round, hours, metric) from its rows; implied by --budget-hours / --target-metric")
     a = ap.parse_args()
     if a.working_size is not None and a.working_size < 1:
         ap.error(f"--working-size {a.working_size}: the length of the shorter side, at least 1")
+    live = a.budget_hours is not None or a.target_metric is not None
+    if (live or a.rank) and a.multi_object:
+        ap.error("--rank / --budget-hours / --target-metric rank the reference's per-object sessions: --multi-object is refused")
+    if live and a.policy == "upper_bound_mask":
+        ap.error("--budget-hours / --target-metric refuse upper_bound_mask: its trials would multiply the cost of every look-ahead round")
     spec = POLICY_TABLE[a.policy]
     typed = "annotation_types" in spec.needs
     if a.annotation_types and "agent" in spec.needs:
@@ -542,9 +580,22 @@ def main():
         from .agent import ActorCritic, PPOAgent
         agent = (PPOAgent(state_dict=synth.recipe_state_dict(ActorCritic(), seed=5)) if a.synthetic_weights else PPOAgent(model_path=a.agent_weights))
     out = os.path.join("Experiments", a.db, "_".join([a.policy] + (sorted(a.annotation_types) if typed else [])) + ".csv")
-    rows = run(a.root, a.imset, out, prop, fuse, a.policy, a.rounds, qnet=qnet, lanes=a.lanes, multi_object=a.multi_object,
-               share_frames=not a.no_share_frames, annotator=a.annotator if "annotator" in spec.needs else None, annotation_types=a.annotation_types, agent=agent,
-               working_size=a.working_size)
+    kw = dict(qnet=qnet, lanes=a.lanes, multi_object=a.multi_object, share_frames=not a.no_share_frames, annotator=a.annotator if "annotator" in spec.needs else None,
+              annotation_types=a.annotation_types, agent=agent, working_size=a.working_size)
+    ref_csv, rank_csv = out[:-4] + "_reference.csv", out[:-4] + "_ranking.csv"
+    if live:
+        from . import budget
+        rows, hours, points, _ = budget.run_ranked(a.root, a.imset, out, prop, fuse, a.policy, a.rounds, budget_hours=a.budget_hours, target_metric=a.target_metric,
+                                                   gamma=a.gamma, reference_csv=ref_csv, ranking_csv=rank_csv, **kw)
+        report_and_leave(f"{len(rows)} committed rounds, {hours[-1]:.3f} annotation hours, metric {points[-1]:.4f} -> {out}, {ref_csv}, {rank_csv}")
+        return
+    rows = run(a.root, a.imset, out, prop, fuse, a.policy, a.rounds, **kw)
+    if a.rank:
+        import torch.distributed as dist
+        if not dist.is_initialized() or dist.get_rank() == 0:
+            from . import budget
+            budget.rank_rows(rows, a.policy, ClipDataset(a.root, a.imset).object_names, a.annotation_types, a.gamma, ref_csv, rank_csv)
+            out = f"{out}, {ref_csv}, {rank_csv}"
     report_and_leave(f"{len(rows)} rounds -> {out}")
 
 

@@ -4,8 +4,9 @@ Own counterpart of the reference's session loops - the mask policies ``interacti
 ``interactions/mulitple_annotations.py:104-283,307-378`` - and of their helpers ``initialize`` / ``not_avail_frames`` /
 ``eval_processor_metric`` (``interactions/eval.py:27-117``).  The reference writes the loop out once per policy; here a policy is a
 ``SessionPolicy`` record - how a frame gets its mask, what else may be done to a frame, how the next frame is chosen, which stop rule
-applies - and ``annotation_session`` is the loop.  ``fq_driver.oracle_rounds`` and ``eval_driver.run_policy`` / ``run_typed_policy`` /
-``run_eva_vos`` build the records; nothing here knows a policy by name."""
+applies - and ``annotation_session`` is the loop (``annotation_rounds``: the same loop, suspended between its rounds).
+``fq_driver.oracle_rounds`` and ``eval_driver.run_policy`` / ``run_typed_policy`` / ``run_eva_vos`` build the records; nothing here knows a
+policy by name."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -63,6 +64,83 @@ class SessionPolicy:
     check_available: bool = True
 
 
+class annotation_rounds:
+    """``annotation_session``'s loop, suspended between its rounds: ``step()`` runs the next scored round - it walks the round counter past
+    the rounds the rules below skip, with the same calls in the same order as the loop written out - and returns False, having run nothing,
+    when none is left.  ``ses`` is the running result (what ``annotation_session`` returns, as of the rounds run so far; ``costs[-1]`` is
+    the last step's seconds), ``more()`` says whether another ``step()`` would run a round, without running it and without changing the
+    session (the stop rules only ever get stricter as the counter grows, so the next counter value decides; it may fetch the quality rows
+    once more).  Nothing outside the arguments is touched: sessions stepped in turn give what each gives run straight through."""
+
+    def __init__(self, processor, scorer, T: int, rounds: int, policy: "SessionPolicy", stats: dict = None):
+        self.processor, self.scorer, self.T, self.rounds, self.policy, self.stats = processor, scorer, T, rounds, policy, stats
+        self.empty = scorer.empty_host
+        self.valid = set(np.where(~self.empty)[0].tolist())          # frames that can be annotated at all
+        self.types = np.zeros(T, np.int64)
+        self.annots = [dict(annotations=[], click_labels=None, click_coords=None, bbox=None, sam_logits=None) for _ in range(T)]
+        self.frames, self.done_types, self.costs, self.actions, self.gens = [0], [], [], [], []
+        self.gen, self.pending, self.r = None, 0, 0
+        self.seen = stats.get("propagated_frames", 0) if stats is not None else 0
+
+    def _skipped(self, r: int) -> bool:
+        policy, costs = self.policy, self.costs
+        if self.pending is None or not (self.types != 1).any():
+            return True
+        # the reference's two stop rules for r >= T
+        if r >= self.T and policy.stop_at_T:                                                        # interactions/mask.py:16
+            return True
+        if (r >= self.T or policy.stop_when_perfect) and costs and float(np.min(self.scorer.qualities()[-1])) == 1.0:   # interactions/mulitple_annotations.py:117
+            return True
+        return bool(policy.check_available and costs and not (self.valid - set(self.frames)))
+
+    def more(self) -> bool:
+        return self.r < self.rounds and not self._skipped(self.r + 1)
+
+    def step(self) -> bool:
+        while self.r < self.rounds:
+            self.r += 1
+            if not self._skipped(self.r):
+                self._round(self.r)
+                return True
+        return False
+
+    def _round(self, r: int):
+        processor, scorer, policy, stats, types, annots, frames = self.processor, self.scorer, self.policy, self.stats, self.types, self.annots, self.frames
+        frame = self.pending
+        if r > 1 and policy.action is not None:
+            mask, cost, action, logits, clicks, labels, bbox = policy.action(frame, self.gen, annots[frame])
+        else:
+            mask, cost, action = None, SKIP_SECONDS if r > 1 and self.empty[frame] else MASK_SECONDS, "mask"
+        if action == "mask":
+            types[frame] = 1
+            interaction = policy.mask_of(frame)
+        else:
+            types[frame] = 2
+            interaction = mask.reshape(policy.mask_of(frame).shape).float()
+            scorer.set_annotation(frame, mask)
+            annots[frame].update(click_labels=labels, click_coords=clicks, bbox=bbox, sam_logits=logits)
+        annots[frame]["annotations"].append(action)
+        processor.interact(interaction, frame, download=False, **policy.interact_kw)
+        if stats is not None:
+            stats["propagated_frames"] = stats.get("propagated_frames", 0) + processor.stats()["frames"]
+            stats["interactions"] = stats.get("interactions", 0) + 1
+        self.done_types.append(int(types[frame]))
+        worst, self.gen = scorer.score(processor, frames, keep_gen=policy.keep_gen, **(dict(types=self.done_types) if policy.action is not None else {}))
+        self.costs.append(cost)
+        self.actions.append(action)
+        self.gens.append(self.gen)
+        self.pending = policy.choose_frame(worst, types, self.gen, frames)
+        if self.pending is not None:
+            frames.append(int(self.pending))
+
+    @property
+    def ses(self) -> dict:
+        n, frames, stats = len(self.costs), self.frames, self.stats
+        return dict(frames=frames[:n], types=self.done_types, costs=self.costs, actions=self.actions, gens=self.gens,
+                    pending=self.pending if len(frames) > n else None, chosen=frames,
+                    propagated_frames=stats.get("propagated_frames", 0) - self.seen if stats is not None else None)
+
+
 def annotation_session(processor, scorer, T: int, rounds: int, policy: SessionPolicy, stats: dict = None) -> dict:
     """The annotation-session loop of every policy.  Round 1 annotates frame 0 with its mask at 80 s; round r > 1 annotates the frame chosen
     last: with its mask (80 s, or 3 s on a frame without the object) or, where the policy has an ``action``, with what that returns.
@@ -79,52 +157,41 @@ def annotation_session(processor, scorer, T: int, rounds: int, policy: SessionPo
     Returns dict(frames, types, costs, actions, gens: per scored round the annotated frame, its type (1 / 2), the seconds, the action and
     the evaluated masks; pending: the frame chosen last, or None; chosen: frames + the pending one; propagated_frames: what this session
     added to ``stats``)."""
-    empty = scorer.empty_host
-    valid = set(np.where(~empty)[0].tolist())                   # frames that can be annotated at all
-    types = np.zeros(T, np.int64)
-    annots = [dict(annotations=[], click_labels=None, click_coords=None, bbox=None, sam_logits=None) for _ in range(T)]
-    frames, done_types, costs, actions, gens = [0], [], [], [], []
-    gen, pending = None, 0
-    seen = stats.get("propagated_frames", 0) if stats is not None else 0
-    for r in range(1, rounds + 1):
-        if pending is None or not (types != 1).any():
-            continue
-        # the reference's two stop rules for r >= T
-        if r >= T and policy.stop_at_T:                                                             # interactions/mask.py:16
-            continue
-        if (r >= T or policy.stop_when_perfect) and costs and float(np.min(scorer.qualities()[-1])) == 1.0:     # interactions/mulitple_annotations.py:117
-            continue
-        if policy.check_available and costs and not (valid - set(frames)):
-            continue
-        frame = pending
-        if r > 1 and policy.action is not None:
-            mask, cost, action, logits, clicks, labels, bbox = policy.action(frame, gen, annots[frame])
-        else:
-            mask, cost, action = None, SKIP_SECONDS if r > 1 and empty[frame] else MASK_SECONDS, "mask"
-        if action == "mask":
-            types[frame] = 1
-            interaction = policy.mask_of(frame)
-        else:
-            types[frame] = 2
-            interaction = mask.reshape(policy.mask_of(frame).shape).float()
-            scorer.set_annotation(frame, mask)
-            annots[frame].update(click_labels=labels, click_coords=clicks, bbox=bbox, sam_logits=logits)
-        annots[frame]["annotations"].append(action)
-        processor.interact(interaction, frame, download=False, **policy.interact_kw)
-        if stats is not None:
-            stats["propagated_frames"] = stats.get("propagated_frames", 0) + processor.stats()["frames"]
-            stats["interactions"] = stats.get("interactions", 0) + 1
-        done_types.append(int(types[frame]))
-        worst, gen = scorer.score(processor, frames, keep_gen=policy.keep_gen, **(dict(types=done_types) if policy.action is not None else {}))
-        costs.append(cost)
-        actions.append(action)
-        gens.append(gen)
-        pending = policy.choose_frame(worst, types, gen, frames)
-        if pending is not None:
-            frames.append(int(pending))
-    n = len(costs)
-    return dict(frames=frames[:n], types=done_types, costs=costs, actions=actions, gens=gens, pending=pending if len(frames) > n else None, chosen=frames,
-                propagated_frames=stats.get("propagated_frames", 0) - seen if stats is not None else None)
+    session = annotation_rounds(processor, scorer, T, rounds, policy, stats)
+    while session.step():
+        pass
+    return session.ses
+
+
+class SteppedSession:
+    """What a ``run_*(..., steps=True)`` hands back instead of its result: the suspended session.  ``step()`` runs one scored round (False:
+    none was left), ``more()`` says whether another would run, ``costs`` are the seconds of the rounds run so far, ``result()`` is what the
+    ``run_*`` would have returned had the session ended after those rounds, ``close()`` gives the engine back as the ``run_*`` found it."""
+
+    def __init__(self, rounds: annotation_rounds, result: Callable, close: Callable = None):
+        self.rounds, self._result, self._close = rounds, result, close
+        self.step, self.more = rounds.step, rounds.more
+
+    @property
+    def costs(self):
+        return self.rounds.costs
+
+    def result(self) -> dict:
+        return self._result(self.rounds.ses)
+
+    def close(self):
+        if self._close is not None:
+            self._close, close = None, self._close
+            close()
+
+    def run(self) -> dict:
+        """Straight through to the end: the ``run_*`` without ``steps``."""
+        try:
+            while self.step():
+                pass
+        finally:
+            self.close()
+        return self.result()
 
 
 def session_result(scorer, ses: dict) -> dict:
