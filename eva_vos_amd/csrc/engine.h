@@ -7,6 +7,7 @@
 #include <memory>
 #include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/stcn_hip.h"
@@ -38,6 +39,71 @@ int make_wino_fusion12(Model &m, ConvW &cw, const std::vector<float> &w_host);  
             return STCN_E_HIP;                                                             \
         }                                                                                  \
     } while (0)
+#define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+
+// ---- owners of device resources: move-only, creation returns the hipError_t, the destructor gives the resource back, and each converts
+// to its raw pointer / handle so that a use site reads as with the raw one.  Whoever destroys an owner has drained the streams that may
+// still use the resource (~stcn_engine, ~stcn_stage) - or hands the buffer to a RetireQueue instead.
+template <class T = void>
+struct PoolBuf {                           // a buffer of the device pool
+    T *p = nullptr;
+    PoolBuf() = default;
+    PoolBuf(PoolBuf &&o) noexcept : p(o.release()) {}
+    template <class U> PoolBuf(PoolBuf<U> &&o) noexcept : p(o.release()) {}       // typed -> untyped, on the way into a RetireQueue
+    PoolBuf &operator=(PoolBuf &&o) noexcept { if (this != &o) { reset(); p = o.release(); } return *this; }
+    ~PoolBuf() { reset(); }
+    hipError_t alloc(size_t bytes) { reset(); return pool_malloc((void **)&p, bytes); }
+    void reset() { pool_free(p); p = nullptr; }
+    T *release() { T *q = p; p = nullptr; return q; }
+    operator T *() const { return p; }
+};
+struct Event {                             // timing disabled
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    ~Event() { if (ev) (void)hipEventDestroy(ev); }
+    hipError_t create() { return hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+    operator hipEvent_t() const { return ev; }
+};
+struct Stream {                            // non-blocking
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&) = delete;
+    ~Stream() { reset(); }
+    void reset() { if (s) (void)hipStreamDestroy(s); s = nullptr; }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+// Buffers that work already enqueued on a stream may still use: they go back to the pool once ONE event, recorded on that stream behind
+// the latest retirement, has fired.  When to collect, whether to wait and what to do without an event stay with the caller.
+struct RetireQueue {
+    std::vector<std::pair<PoolBuf<>, size_t>> bufs;      // (buffer, bytes it has room for)
+    Event ev;
+    // records the event on s, creating it at the first use; on failure *what names the step and nothing has changed
+    hipError_t mark(hipStream_t s, const char **what) {
+        *what = "event create";
+        if (!ev) { const hipError_t er = ev.create(); if (er != hipSuccess) return er; }
+        *what = "event record";
+        return hipEventRecord(ev, s);
+    }
+    void push(PoolBuf<> b, size_t bytes = 0) { bufs.emplace_back(std::move(b), bytes); }      // after mark()
+    void collect(bool wait) {              // frees everything once the event has fired: waits for it, or leaves it for later (never blocks)
+        if (bufs.empty()) return;
+        if (wait) (void)hipEventSynchronize(ev);
+        else if (hipEventQuery(ev) != hipSuccess) return;
+        bufs.clear();
+    }
+    // the smallest retired buffer with room for `bytes`, taken out of the queue (for reuse on the SAME stream: ordered behind its last use)
+    bool take_fitting(size_t bytes, PoolBuf<> *b, size_t *cap) {
+        size_t best = bufs.size();
+        for (size_t i = 0; i < bufs.size(); ++i)
+            if (bufs[i].second >= bytes && (best == bufs.size() || bufs[i].second < bufs[best].second)) best = i;
+        if (best == bufs.size()) return false;
+        *b = std::move(bufs[best].first); *cap = bufs[best].second;
+        bufs.erase(bufs.begin() + (long)best);
+        return true;
+    }
+};
 
 struct ConvW {
     float *w = nullptr, *bias = nullptr;   // device: [Cout][Kp], [Cout]
@@ -70,6 +136,15 @@ struct Dims {
         npix = (long)nh * nw; hw2 = h2 * w2; hw4 = h4 * w4; hw8 = h8 * w8; hw16 = h16 * w16;
     }
 };
+// A key-cache slot: ten fields of one frame, in this order, each starting at a multiple of 4 floats (off) - the one statement of it
+enum { SLOT_K16, SLOT_MSQ, SLOT_F16_THIN, SLOT_F16, SLOT_S8, SLOT_S4, SLOT_DTHIN, SLOT_CTHIN, SLOT_VD, SLOT_VC, SLOT_FIELDS };
+struct SlotLayout { size_t off[SLOT_FIELDS], ext[SLOT_FIELDS], total; };      // floats
+inline SlotLayout slot_layout(const Dims &d) {
+    const size_t q = (size_t)d.hw16;
+    SlotLayout l{{}, {q * 64, (q + 3) / 4 * 4, q * 512, q * 1024, (size_t)d.hw8 * 512, (size_t)d.hw4 * 256, q * 512, q * 512, q * 512, q * 512}, 0};
+    for (int f = 0; f < SLOT_FIELDS; ++f) { l.off[f] = l.total; l.total += l.ext[f]; }
+    return l;
+}
 
 // per-kernel-class accounting (flops always; device time when profiling is on)
 struct Prof {
@@ -127,15 +202,16 @@ struct Work {
     float *pooled = nullptr, *amap = nullptr, *attn = nullptr;   // attention read
     float *cand_v = nullptr; int32_t *cand_i = nullptr, *cand_n = nullptr;   // memory-read chunk winners
     float *gmax = nullptr, *tau = nullptr;                       // memory-read group maxima / thresholds
-    int32_t *centre = nullptr;          // kernelized read: [group][memread_centre_stride(bank rows)] row centres; grows with the bank (bank_reserve), not in allocs
+    int32_t *centre = nullptr;          // kernelized read: [group][memread_centre_stride(bank rows)] row centres; grows with the bank (bank_reserve), not owned
     float *qk = nullptr;                // [group][hw16][64] queries of a decode group
     float *vin = nullptr;               // value-encoder packed input [k][npix][8]
     Prof *prof = nullptr;
     Knobs kn = Knobs::from_env();       // launch-level tunables, read once when the workspace is made
     int conv_cls = STCN_K_CONV;         // accounting class of the conv GEMMs launched through this workspace (fusion_logit switches it)
-    std::vector<void *> allocs;
+    std::vector<PoolBuf<>> owned;       // what init() allocated; the pointers above are views (the test rigs of hooks.cpp lend wino_v / splitk of their own)
+    Work() = default;
+    Work(const Work &) = delete;        // every buffer has one owner
     int init(int nh, int nw, int k, int key_batch = 1, int group = 1);   // group: frames decoded per pass (k == 1)
-    void release();
 };
 
 // ---- stages (enqueue only) -----------------------------------------------------------------
@@ -221,7 +297,7 @@ struct stcn_engine {
     int lw = 0, uw = 0, lh = 0, uh = 0;
     stcn::Dims d{};
     float *images4 = nullptr;          // [T][nh][nw][4]; immutable after create, shared with clones
-    std::shared_ptr<void> images_owner;  // frees images4 with the last engine that uses it
+    std::shared_ptr<stcn::PoolBuf<float>> images_owner;  // frees images4 with the last engine that uses it
     float *prob = nullptr;             // caller-owned [k+1][T][npix]
     uint8_t *masks = nullptr;          // caller-owned [T][npix]
     // key-feature cache
@@ -229,35 +305,35 @@ struct stcn_engine {
     std::vector<int> slot_of;          // frame -> slot or -1
     std::vector<char> vparts_ready;    // frame -> value-encoder frame parts (vd, vc) are in its slot
     int n_cached = 0;
-    float *cache = nullptr; size_t slot_floats = 0;
-    double *gram_scratch = nullptr;    // stcn_engine_frame_distances: partial Gram tiles (frame_gram_scratch_bytes), taken from the pool at the first call
+    stcn::PoolBuf<float> cache;
+    stcn::SlotLayout slot{}; size_t slot_floats = 0;   // slot_floats = slot.total
+    stcn::PoolBuf<double> gram_scratch;    // stcn_engine_frame_distances: partial Gram tiles (frame_gram_scratch_bytes), taken from the pool at the first call
     // memory bank: rows = slots * hw16
     int bank_cap = 0, n_certain = 0;
-    float *bank_k = nullptr, *bank_msq = nullptr, *bank_v = nullptr;
-    int32_t *bank_centre = nullptr;    // kernelized read (model km > 0): the row-centre scratch of work / work2, one block each, sized for bank_cap
-    std::vector<void *> retired;       // bank buffers replaced by a larger generation, freed once retire_ev has fired
-    hipEvent_t retire_ev = nullptr;
+    stcn::PoolBuf<float> bank_k, bank_msq, bank_v;
+    stcn::PoolBuf<int32_t> bank_centre;    // kernelized read (model km > 0): the row-centre scratch of work / work2, one block each, sized for bank_cap
+    stcn::RetireQueue retired;         // bank buffers replaced by a larger generation
     std::set<int> interacted;
-    float *mask_pad = nullptr, *pos = nullptr, *neg = nullptr;   // [k+1][npix] each
+    stcn::PoolBuf<float> mask_pad, pos, neg;   // [k+1][npix] each
     stcn::Work work;
     // key-encoder look-ahead: frames ahead of the decode chain are encoded on a side stream
-    hipStream_t side = nullptr;
+    stcn::Stream side;
     stcn::Work work_side;
     // round 6: the BACKWARD sweep of an interaction on its own stream and workspace, concurrently with the forward sweep (the two sweeps
     // of do_pass share nothing but the certain memory, which neither writes: inference_core.py:250-253 runs them one after the other).
     // Its temporary bank slots grow DOWNWARD from bank_lo, in front of the certain slots, the forward sweep's upward behind them: each
     // sweep reads one contiguous row range [its temporaries | certain] / [certain | its temporaries].  One video in flight only (same
     // switch as the key-encoder look-ahead); clips longer than the key cache (flush-all policy) keep the serial order.
-    hipStream_t stream2 = nullptr;
+    stcn::Stream stream2;
     stcn::Work work2;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    stcn::Event ev_fork, ev_join;
     int bank_lo = 0;                     // bank slots in front of the certain slots (0: serial sweeps)
-    std::vector<hipEvent_t> key_ready;   // per frame: recorded on `side` after its encode_key
+    std::vector<stcn::Event> key_ready;   // per frame: recorded on `side` after its encode_key
     std::vector<char> key_pending;       // per frame: main stream has not yet waited on key_ready
     int lookahead = 0;
     // FusionNet of a decoded group on the side stream (rounds >= 2: the side stream has no keys to encode), two agg buffers
     bool fuse_side = false;
-    hipEvent_t ev_dec[2] = {nullptr, nullptr}, ev_fuse[2] = {nullptr, nullptr};
+    stcn::Event ev_dec[2], ev_fuse[2];
     char fuse_pending[2] = {0, 0};       // ev_fuse[b] is recorded and the main stream has not waited for it yet
     int agg_buf = 0;
     int key_batch = 1;                   // frames per key-encoder pass (env STCN_KEY_BATCH)
@@ -269,12 +345,12 @@ struct stcn_engine {
     // undo journal (stcn_engine_set_undo): the last undo_depth interactions, oldest first.  An entry holds what its interaction was about
     // to overwrite - frames [f0, f0 + n) of the k + 1 prob rows, then the same frames of masks, in ONE pool buffer sized to that span - and the
     // host bookkeeping to put back.  A dropped entry's buffer is RETIRED: copies out of / into it may still be in flight on the engine's
-    // stream, so it is reused by this engine's next save (same stream: ordered) or handed to the pool once undo_ev, recorded behind the
-    // latest retirement, has fired.  Depth 0: all of this stays empty and nothing is allocated, recorded or enqueued.
-    struct UndoEntry { int idx, f0, n, n_certain0; bool was_interacted; void *buf; size_t bytes; };
+    // stream, so it is reused by this engine's next save (same stream: ordered) or handed to the pool once the event of undo_retired,
+    // recorded behind the latest retirement, has fired.  Depth 0: all of this stays empty and nothing is allocated, recorded or enqueued.
+    struct UndoEntry { int idx, f0, n, n_certain0; bool was_interacted; stcn::PoolBuf<> buf; size_t bytes; };
     int undo_depth = 0;
     std::deque<UndoEntry> journal;
-    std::vector<std::pair<void *, size_t>> undo_retired;
-    hipEvent_t undo_ev = nullptr;
-    std::vector<void *> allocs;
+    stcn::RetireQueue undo_retired;
+    // drains the caller's stream (the device when it is null), then side, then stream2: only then do the members above give anything back
+    ~stcn_engine();
 };

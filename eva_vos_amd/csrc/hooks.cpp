@@ -10,14 +10,13 @@
 #include "engine.h"
 
 using namespace stcn;
-#define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 namespace {
 struct TmpWork {
     Work w;
     int rc;
     TmpWork(int nh, int nw, int k) { rc = w.init(nh, nw, k); }
-    ~TmpWork() { (void)hipDeviceSynchronize(); w.release(); }
+    ~TmpWork() { (void)hipDeviceSynchronize(); }      // then w gives its buffers back
 };
 struct DevBuf {
     float *p = nullptr;

@@ -8,7 +8,6 @@
 #include "engine.h"
 
 using namespace stcn;
-#define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 struct stcn_stage {
     const Model *model = nullptr;
@@ -16,17 +15,18 @@ struct stcn_stage {
     int max_k = 0;
     Work w;                              // sized for max_k objects; w.k and the planning capacity w.wino_v_floats are set per call (stage_batch)
     size_t v_alloc = 0;                  // Winograd V floats allocated
-    float *img4 = nullptr;               // [npix][4] the call's frame
-    float *k16 = nullptr, *thin = nullptr, *f16 = nullptr, *f8 = nullptr, *f4 = nullptr;     // the frame's features as rows
-    float *s8 = nullptr, *s4 = nullptr;  // decoder skip convs of f8 / f4
-    float *val = nullptr;                // [max_k][hw16][512] encode_value's output as rows
-    float *qsq = nullptr;                // [hw16 + MEMREAD_MSQ_PAD] |k16|^2 (segment: of the queries, km; attention: of the memory key)
-    float *mk1 = nullptr;                // [hw16][64] attention's memory key
+    PoolBuf<float> img4;                 // [npix][4] the call's frame
+    PoolBuf<float> k16, thin, f16, f8, f4;     // the frame's features as rows
+    PoolBuf<float> s8, s4;               // decoder skip convs of f8 / f4
+    PoolBuf<float> val;                  // [max_k][hw16][512] encode_value's output as rows
+    PoolBuf<float> qsq;                  // [hw16 + MEMREAD_MSQ_PAD] |k16|^2 (segment: of the queries, km; attention: of the memory key)
+    PoolBuf<float> mk1;                  // [hw16][64] attention's memory key
     // bank staging of segment: the memory as rows, grown geometrically (stage_grow) to the largest (rows, objects) seen
     long bank_rows = 0; int bank_k = 0;
-    float *bank_key = nullptr, *bank_msq = nullptr, *bank_val = nullptr;
-    int32_t *centre = nullptr;           // kernelized read: row centres of one frame of queries
-    std::vector<void *> allocs;          // everything but the bank staging
+    PoolBuf<float> bank_key, bank_msq, bank_val;
+    PoolBuf<int32_t> centre;             // kernelized read: row centres of one frame of queries
+    // the buffers go back to the pool: nothing of this context may still run
+    ~stcn_stage() { if (model) (void)hipSetDevice(model->device); (void)hipStreamSynchronize(stream); }
 };
 
 namespace stcn {
@@ -35,16 +35,6 @@ long stage_grow(long cap, long need) { return need <= cap ? cap : std::max(need,
 }  // namespace stcn
 
 namespace {
-int stage_alloc(stcn_stage *s, float **p, size_t floats) {
-    HIPCHK(pool_malloc((void **)p, floats * sizeof(float)));
-    s->allocs.push_back(*p);
-    return STCN_OK;
-}
-void bank_release(stcn_stage *s) {
-    for (void *p : {(void *)s->bank_key, (void *)s->bank_msq, (void *)s->bank_val, (void *)s->centre}) pool_free(p);
-    s->bank_key = s->bank_msq = s->bank_val = nullptr; s->centre = nullptr;
-    s->bank_rows = 0; s->bank_k = 0;
-}
 // room for a memory of `rows` rows and k objects.  Growing waits for the context's stream first (earlier calls may still read the old
 // staging, and a buffer handed back to the pool can be another context's the next moment) - the one place a stage call waits at all
 int bank_reserve(stcn_stage *s, long rows, int k) {
@@ -52,11 +42,12 @@ int bank_reserve(stcn_stage *s, long rows, int k) {
     const long nr = stage_grow(s->bank_rows, rows);
     const int nk = (int)std::min<long>(STCN_MAX_OBJECTS, stage_grow(s->bank_k, k));
     HIPCHK(hipStreamSynchronize(s->stream));
-    bank_release(s);
-    HIPCHK(pool_malloc((void **)&s->bank_key, (size_t)nr * 64 * 4));
-    HIPCHK(pool_malloc((void **)&s->bank_msq, ((size_t)nr + MEMREAD_MSQ_PAD) * 4));
-    HIPCHK(pool_malloc((void **)&s->bank_val, (size_t)nk * nr * 512 * 4));
-    HIPCHK(pool_malloc((void **)&s->centre, (size_t)memread_centre_stride((int)nr) * 4));
+    s->bank_key.reset(); s->bank_msq.reset(); s->bank_val.reset(); s->centre.reset();
+    s->bank_rows = 0; s->bank_k = 0;                   // a failure below leaves no staging
+    HIPCHK(s->bank_key.alloc((size_t)nr * 64 * 4));
+    HIPCHK(s->bank_msq.alloc(((size_t)nr + MEMREAD_MSQ_PAD) * 4));
+    HIPCHK(s->bank_val.alloc((size_t)nk * nr * 512 * 4));
+    HIPCHK(s->centre.alloc((size_t)memread_centre_stride((int)nr) * 4));
     s->bank_rows = nr; s->bank_k = nk;
     return STCN_OK;
 }
@@ -90,28 +81,21 @@ int stcn_stage_create(const stcn_model *m, int nh, int nw, int max_objects, void
     if (max_objects < 1 || max_objects > STCN_MAX_OBJECTS) { set_error("stcn_stage_create: max_objects=%d outside 1..%d", max_objects, STCN_MAX_OBJECTS); return STCN_E_INVALID; }
     if (!m || !out) { set_error("stcn_stage_create: null arguments"); return STCN_E_INVALID; }
     HIPCHK(hipSetDevice(m->m.device));
-    stcn_stage *s = new stcn_stage();
+    std::unique_ptr<stcn_stage> s(new stcn_stage());       // a failure below destroys it: whatever it took so far goes back
     s->model = &m->m; s->stream = (hipStream_t)stream; s->max_k = max_objects;
-    int rc = s->w.init(nh, nw, max_objects);
+    RC(s->w.init(nh, nw, max_objects));
     s->v_alloc = s->w.wino_v_floats;
     const Dims &d = s->w.d;
     const size_t sizes[] = {(size_t)d.npix * 4, (size_t)d.hw16 * 64, (size_t)d.hw16 * 512, (size_t)d.hw16 * 1024, (size_t)d.hw8 * 512, (size_t)d.hw4 * 256,
                             (size_t)d.hw8 * 512, (size_t)d.hw4 * 256, (size_t)max_objects * d.hw16 * 512, (size_t)d.hw16 + MEMREAD_MSQ_PAD, (size_t)d.hw16 * 64};
-    float **ptrs[] = {&s->img4, &s->k16, &s->thin, &s->f16, &s->f8, &s->f4, &s->s8, &s->s4, &s->val, &s->qsq, &s->mk1};
-    for (size_t i = 0; !rc && i < sizeof(sizes) / sizeof(sizes[0]); ++i) rc = stage_alloc(s, ptrs[i], sizes[i]);
-    if (rc) { stcn_stage_destroy(s); return rc; }
-    *out = s;
+    PoolBuf<float> *bufs[] = {&s->img4, &s->k16, &s->thin, &s->f16, &s->f8, &s->f4, &s->s8, &s->s4, &s->val, &s->qsq, &s->mk1};
+    for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) HIPCHK(bufs[i]->alloc(sizes[i] * sizeof(float)));
+    *out = s.release();
     return STCN_OK;
 }
 
 int stcn_stage_destroy(stcn_stage *s) {
-    if (!s) return STCN_OK;
-    (void)hipSetDevice(s->model->device);
-    (void)hipStreamSynchronize(s->stream);            // the buffers go back to the pool: nothing of this context may still run
-    bank_release(s);
-    for (void *p : s->allocs) pool_free(p);
-    s->w.release();
-    delete s;
+    if (s) delete s;
     return STCN_OK;
 }
 

@@ -109,6 +109,17 @@ def _context(model, nh: int, nw: int, k: int, device) -> C.c_void_p:
         return hit[0]
 
 
+def _destroy_contexts(model) -> int:
+    """Destroys every cached stage context of ``model`` (each waits for its stream); returns how many there were.  The next stage call
+    makes a new one."""
+    with _LOCK:
+        ctxs = model.__dict__.get("_stage_contexts", {})
+        n = len(ctxs)
+        while ctxs:
+            ctxs.popitem()[1][2]()
+    return n
+
+
 def _prop_model(prop_net, device):
     return _model_for(prop_net, None, device.index, _top_k_of(prop_net), _km_of(prop_net))
 

@@ -449,6 +449,9 @@ int stcn_memread_scratch(int Q, int64_t *sizes5);
  * per buffer would synchronise the device under the other videos in flight).  STCN_POOL_GB bounds the pool (default 64, 0 = off);
  * this call returns everything it holds to the driver. */
 int stcn_pool_release(void);
+/* What the pool has handed out and not got back (buffers, bytes of their size classes) and what it keeps parked, over all devices;
+ * null pointers are skipped.  With STCN_POOL_GB=0 nothing is tracked: all zero.  Lets tests show that destroyed engines left nothing behind. */
+int stcn_pool_stats(int64_t *live_buffers, int64_t *live_bytes, int64_t *cached_bytes);
 
 /* Test hook (fault injection): the n-th kernel-launch status check made by the CALLING THREAD from now on reports a
  * failure (n = 0 disarms).  Used to show that a failing stcn_interact leaves the engine in a defined state.

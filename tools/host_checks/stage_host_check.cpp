@@ -56,6 +56,34 @@ int main() {
     long cap = 0; int grows = 0;
     for (long rows = 80; rows <= 8000; rows += 80) { const long c = stcn::stage_grow(cap, rows); EXPECT(c >= rows && c >= cap); if (c != cap) ++grows; cap = c; }
     EXPECT(grows <= 8 && cap < 2 * 8000);
+    // the key-cache slot layout: ten fields, increasing, each at a multiple of 4 floats, nothing behind the last one, and as many floats as
+    // the formula engine_alloc_common used to spell out beside slot_ptrs' walk
+    const int frames[][2] = {{128, 160}, {480, 864}, {16, 16}};
+    for (const auto &f : frames) {
+        stcn::Dims dm; dm.set(f[0], f[1]);
+        const stcn::SlotLayout l = stcn::slot_layout(dm);
+        for (int i = 0; i < stcn::SLOT_FIELDS; ++i) {
+            EXPECT(l.off[i] % 4 == 0 && l.ext[i] > 0);
+            if (i) EXPECT(l.off[i] > l.off[i - 1] && l.off[i] >= l.off[i - 1] + l.ext[i - 1]);
+        }
+        EXPECT(l.off[0] == 0 && l.off[stcn::SLOT_VC] + l.ext[stcn::SLOT_VC] == l.total);
+        EXPECT(l.total == (size_t)dm.hw16 * (64 + 512 + 1024) + (size_t)(dm.hw16 + 3) / 4 * 4 + (size_t)dm.hw8 * 512 + (size_t)dm.hw4 * 256 + (size_t)4 * dm.hw16 * 512);
+    }
+    {   // the retire queue hands out the smallest retired buffer that fits, none when nothing fits, and removes exactly what it handed out.
+        // The entries are host addresses that stand for buffers: every one is taken back (release) before an owner could free it
+        static char mem[4];
+        const size_t sizes[4] = {300, 100, 200, 100};
+        stcn::RetireQueue q;
+        for (int i = 0; i < 4; ++i) { stcn::PoolBuf<> b; b.p = &mem[i]; q.push(std::move(b), sizes[i]); }
+        stcn::PoolBuf<> got; size_t cap = 0;
+        EXPECT(!q.take_fitting(301, &got, &cap) && !got && q.bufs.size() == 4);
+        EXPECT(q.take_fitting(150, &got, &cap) && got.release() == &mem[2] && cap == 200 && q.bufs.size() == 3);
+        EXPECT(q.take_fitting(100, &got, &cap) && got.release() == &mem[1] && cap == 100 && q.bufs.size() == 2);      // of two equal ones the older
+        EXPECT(q.bufs[0].first.p == &mem[0] && q.bufs[1].first.p == &mem[3]);
+        EXPECT(q.take_fitting(1, &got, &cap) && got.release() == &mem[3] && cap == 100);
+        EXPECT(!q.take_fitting(301, &got, &cap) && q.take_fitting(300, &got, &cap) && got.release() == &mem[0] && q.bufs.empty());
+        EXPECT(!q.take_fitting(0, &got, &cap));
+    }
     std::printf(failures ? "stage_host_check: %d FAILED\n" : "stage_host_check: all checks passed\n", failures);
     return failures ? 1 : 0;
 }
