@@ -28,6 +28,11 @@ class EngineOpts(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("lookahead", "decode_batch", "key_batch", "fuse_side")]
 
 
+# the int32 of an engine plan in the order of include/stcn_hip.h (STCN_ENGINE_PLAN_INTS of them); stcn_engine_get_plan appends bank_cap
+ENGINE_PLAN_FIELDS = ("n_slots", "lookahead", "lookahead_req", "group", "key_batch", "fuse_side", "dual_sweep", "bank_lo", "bank_initial",
+                      "main_key_batch", "main_group", "has_side", "side_key_batch", "side_group", "second_key_batch", "second_group")
+
+
 class ModelOpts(C.Structure):
     """stcn_model_opts: a non-positive field = not given (top_k: 50; km: the plain read)."""
     _fields_ = [("top_k", C.c_int32), ("km", C.c_float)]
@@ -60,6 +65,8 @@ PROTOTYPES = {
     "stcn_engine_create": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(_P)]),
     "stcn_engine_create_ex": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, C.POINTER(EngineOpts), C.POINTER(_P)]),
     "stcn_engine_get_opts": (_I, [_P, C.POINTER(EngineOpts)]),
+    "stcn_engine_get_plan": (_I, [_P, C.POINTER(C.c_int32), _I]),
+    "stcn_test_engine_plan": (_I, [_I, _I, _I, _I, C.POINTER(EngineOpts), C.POINTER(C.c_int32), _I]),
     "stcn_engine_destroy": (_I, [_P]),
     "stcn_engine_reset": (_I, [_P]),
     "stcn_engine_reset_ex": (_I, [_P, C.c_uint32, C.POINTER(C.c_int32)]),

@@ -263,6 +263,33 @@ struct SweepGroup {
 };
 std::vector<SweepGroup> plan_sweep(int idx, int closest, int mem_freq, int cap);
 constexpr int MAX_DECODE_GROUP = 8;      // the largest cap an engine uses
+// ---- one engine: what it is built with and how its bank is sized, as data
+// The five engine variables, read once (absent: the default) - the environment half of "explicit option, else environment, else default"
+struct EngineEnv {
+    int lookahead = 2, decode_batch = 8, key_batch = 0, fuse_side = 1, dual_sweep = 1;
+    static EngineEnv from_env();         // STCN_LOOKAHEAD, STCN_DECODE_BATCH, STCN_KEY_BATCH, STCN_FUSE_SIDE, STCN_DUAL_SWEEP
+};
+constexpr int KEY_CACHE_SLOTS = 106;     // key_buf holds at most 106 frames (inference_core.py:46,118)
+struct WorkShape { int key_batch, group; };      // what Work::init is given
+struct EnginePlan {
+    int mem_freq = 5;                    // as given to stcn_engine_create: the bank is sized for it
+    int n_slots = 0;                     // key-cache slots: min(T, KEY_CACHE_SLOTS)
+    int lookahead_req = 0;               // look-ahead as asked for: > 0 = one video in flight - the side stream, fuse_side and the dual sweep key on it
+    int lookahead = 0;                   // ... and as it runs: 0 for a clip longer than the key cache (its slots are recycled)
+    int group = 1;                       // frames per memory-read + decoder pass: <= mem_freq (a group ends at the next bank insertion),
+                                         // <= MAX_DECODE_GROUP, objects x frames <= 16 (workspace ~ 0.1 GB each)
+    int key_batch = 1;                   // frames per key-encoder pass: as asked, else max(4, group) - a decode group is key-encoded in one pass; <= 8
+    bool fuse_side = false;              // FusionNet of rounds >= 2 on the side stream: one video in flight and a fusion network
+    bool dual_sweep = false;             // the backward sweep beside the forward one, on stream2 / work2: one video in flight, no cache recycling, T >= 3
+    int bank_lo = 0;                     // bank slots in front of the certain slots: the longest backward sweep's temporaries + 1 spare (0: serial sweeps)
+    int bank_initial = 0;                // slots reserved at create: room for the first 8 interactions (later ones grow the bank)
+    WorkShape main{1, 1}, side{1, 1}, second{1, 1};      // work, work_side, work2 (second exists iff dual_sweep)
+    bool has_side = false;               // the side stream and its workspace exist: look-ahead or fuse_side
+};
+// Pure host code: no HIP call, no getenv, no engine state.  T, k, mem_freq >= 1 as stcn_engine_create checks them.
+EnginePlan plan_engine(int T, int k, int mem_freq, bool has_fuse, const stcn_engine_opts &opts, const EngineEnv &env);
+// the bank slots an engine needs for a sweep over `span` frames beside `certain` certain slots - the one statement of it
+int bank_slots_needed(const EnginePlan &p, int span, int certain);
 // B consecutive frames at once; outputs of frame b at o.<ptr> + b * out_bs
 int encode_key(const Model &m, Work &w, hipStream_t s, const float *img4, const KeyOut &o, int B = 1, long out_bs = 0);
 // vd / vc: cached frame-only halves of fuser.block1 (nullptr: compute the full two-source convs)
@@ -292,16 +319,15 @@ struct stcn_model { stcn::Model m; };
 struct stcn_engine {
     const stcn::Model *model = nullptr;
     hipStream_t stream = nullptr;
-    int T = 0, H = 0, W = 0, k = 0, mem_freq = 5;
-    stcn_engine_opts opts{-1, -1, -1, -1};   // tunables: as given to stcn_engine_create_ex, then resolved (environment / defaults) at create
+    int T = 0, H = 0, W = 0, k = 0;
+    stcn::EnginePlan plan;             // what the tunables resolved to when the engine was created (plan_engine); a clone copies its source's
     int lw = 0, uw = 0, lh = 0, uh = 0;
     stcn::Dims d{};
     float *images4 = nullptr;          // [T][nh][nw][4]; immutable after create, shared with clones
     std::shared_ptr<stcn::PoolBuf<float>> images_owner;  // frees images4 with the last engine that uses it
     float *prob = nullptr;             // caller-owned [k+1][T][npix]
     uint8_t *masks = nullptr;          // caller-owned [T][npix]
-    // key-feature cache
-    int n_slots = 0;
+    // key-feature cache (plan.n_slots slots)
     std::vector<int> slot_of;          // frame -> slot or -1
     std::vector<char> vparts_ready;    // frame -> value-encoder frame parts (vd, vc) are in its slot
     int n_cached = 0;
@@ -321,23 +347,18 @@ struct stcn_engine {
     stcn::Work work_side;
     // round 6: the BACKWARD sweep of an interaction on its own stream and workspace, concurrently with the forward sweep (the two sweeps
     // of do_pass share nothing but the certain memory, which neither writes: inference_core.py:250-253 runs them one after the other).
-    // Its temporary bank slots grow DOWNWARD from bank_lo, in front of the certain slots, the forward sweep's upward behind them: each
+    // Its temporary bank slots grow DOWNWARD from plan.bank_lo, in front of the certain slots, the forward sweep's upward behind them: each
     // sweep reads one contiguous row range [its temporaries | certain] / [certain | its temporaries].  One video in flight only (same
     // switch as the key-encoder look-ahead); clips longer than the key cache (flush-all policy) keep the serial order.
     stcn::Stream stream2;
     stcn::Work work2;
     stcn::Event ev_fork, ev_join;
-    int bank_lo = 0;                     // bank slots in front of the certain slots (0: serial sweeps)
     std::vector<stcn::Event> key_ready;   // per frame: recorded on `side` after its encode_key
     std::vector<char> key_pending;       // per frame: main stream has not yet waited on key_ready
-    int lookahead = 0;
     // FusionNet of a decoded group on the side stream (rounds >= 2: the side stream has no keys to encode), two agg buffers
-    bool fuse_side = false;
     stcn::Event ev_dec[2], ev_fuse[2];
     char fuse_pending[2] = {0, 0};       // ev_fuse[b] is recorded and the main stream has not waited for it yet
     int agg_buf = 0;
-    int key_batch = 1;                   // frames per key-encoder pass (env STCN_KEY_BATCH)
-    int group = 1;                       // frames per memory-read + decoder pass (env STCN_DECODE_BATCH), <= MAX_DECODE_GROUP
     stcn::Prof prof;
     stcn_stats stats{};
     int64_t key_frames = 0;              // frames that went through the key encoder since creation / the last reset (stcn_get_key_frames)

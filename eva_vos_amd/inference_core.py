@@ -489,6 +489,14 @@ class InferenceCore:
         _lib.check(_lib.lib().stcn_engine_get_opts(self._engine, C.byref(o)))
         return {n: getattr(o, n) for n, _ in _lib.EngineOpts._fields_}
 
+    def engine_plan(self) -> dict:
+        """Everything the engine was configured with when it was created (include/stcn_hip.h: stcn_engine_get_plan), and ``bank_cap``, the
+        capacity of its memory bank in slots now."""
+        names = _lib.ENGINE_PLAN_FIELDS + ("bank_cap",)
+        out = (C.c_int32 * len(names))()
+        _lib.check(_lib.lib().stcn_engine_get_plan(self._engine, out, len(names)), "stcn_engine_get_plan")
+        return dict(zip(names, out))
+
     def set_profiling(self, on: bool) -> None:
         _lib.check(_lib.lib().stcn_engine_set_profiling(self._engine, 1 if on else 0))
 

@@ -116,6 +116,25 @@ int stcn_engine_create_ex(const stcn_model *m, int T, int H, int W, int k, int m
 /* The values the engine actually runs with (after the environment / defaults were resolved and clipped: look-ahead is 0 when the
  * clip is longer than the key cache, the decode group never exceeds mem_freq or 16 / k objects, fuse_side needs a fusion network). */
 int stcn_engine_get_opts(const stcn_engine *e, stcn_engine_opts *out);
+/* Everything an engine is configured with, resolved once when it is created (a clone carries its source's, whatever the environment
+ * says by then), as STCN_ENGINE_PLAN_INTS int32 in this order:
+ *   n_slots        key-cache slots: min(T, 106)
+ *   lookahead      as it runs: 0 for a clip longer than the key cache
+ *   lookahead_req  as asked for (option / STCN_LOOKAHEAD / 2): > 0 = one video in flight, what the next three rest on
+ *   group          decode group: option / STCN_DECODE_BATCH / 8, at most mem_freq, 8 and 16 / k objects, at least 1
+ *   key_batch      option / STCN_KEY_BATCH / 0, where <= 0 means max(4, group); at most 8
+ *   fuse_side      lookahead_req > 0, a fusion network, and option / STCN_FUSE_SIDE / 1
+ *   dual_sweep     the backward sweep of an interaction beside the forward one: lookahead_req > 0, 3 <= T <= n_slots, STCN_DUAL_SWEEP (1) != 0
+ *   bank_lo        bank slots in front of the certain slots: (T - 1) / mem_freq + 2 with the dual sweep, else 0
+ *   bank_initial   bank slots reserved at create: bank_lo + (T - 1) / mem_freq + 1 + 8
+ *   main key_batch, main group, has_side, side key_batch, side group, second key_batch, second group
+ *                  what the engine's workspaces are built for; the side one exists when has_side, the second one when dual_sweep
+ * stcn_engine_get_plan writes them for a live engine and one more: the capacity of its memory bank in slots, now (n > STCN_ENGINE_PLAN_INTS).
+ * Test hook stcn_test_engine_plan: the plan an engine of this shape would get under opts (NULL: none given) and the environment as it is
+ * now; has_fuse: the model has a fusion network.  No device call, no GPU needed. */
+#define STCN_ENGINE_PLAN_INTS 16
+int stcn_engine_get_plan(const stcn_engine *e, int32_t *out, int n);
+int stcn_test_engine_plan(int T, int k, int mem_freq, int has_fuse, const stcn_engine_opts *opts, int32_t *out, int n);
 
 /* Back to the state right after stcn_engine_create (same clip): forgets interactions, certain memory and the
  * key-feature cache, re-initialises prob / masks.  Lets a driver reuse one engine's device memory for the

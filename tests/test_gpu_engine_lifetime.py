@@ -8,6 +8,7 @@ import copy
 import ctypes as C
 import gc
 
+import numpy as np
 import pytest
 import torch
 
@@ -127,6 +128,32 @@ def test_failure_paths_return_every_buffer(nets, options):
     assert core.interacted == {5} and core.stats()["frames"] == T - 1
     del core, clone
     assert pool_live() == base
+
+
+def test_a_clone_reserves_the_bank_of_its_source_and_continues_the_session(weights, nets, monkeypatch):
+    """A clone's bank has its source's capacity - not that capacity plus the slots in front of the certain ones once more, which doubled
+    it per generation of clones - and the clone carries the session on exactly as its source does.  T = 9 at mem_freq 1 with the dual
+    sweep: 8 + 2 slots in front (bank_lo), 9 behind for a whole-clip sweep, 8 certain ones = 27, so a bank of 32."""
+    from eva_vos_amd.params import PropagationNetwork
+    from mivos.inference_core import InferenceCore
+    for name in ("STCN_LOOKAHEAD", "STCN_DUAL_SWEEP"):
+        monkeypatch.delenv(name, raising=False)
+    prop = PropagationNetwork(top_k=16)          # 64 x 64 pixels: 16 bank rows per frame
+    prop.load_state_dict(weights[0], strict=True)
+    n, s = 9, 64
+    img, msk = synth.synthetic_clip(n, s, s, seed=31).cuda(), synth.synthetic_mask(n, s, s, 1, seed=32).cuda()
+    src = InferenceCore(prop.eval(), nets[1], img, 1, mem_freq=1, engine_options={"lookahead": 2})
+    plan = src.engine_plan()
+    assert (plan["dual_sweep"], plan["bank_lo"], plan["bank_initial"], plan["bank_cap"]) == (1, 10, 27, 32)
+    src.interact(msk[:, 2], 2, download=False)
+    clone = copy.deepcopy(src)
+    assert clone.engine_plan() == plan
+    grandchild = copy.deepcopy(clone)
+    assert grandchild.engine_plan() == plan
+    for f in (6, 4):
+        assert np.array_equal(clone.interact(msk[:, f], f), src.interact(msk[:, f], f))
+        assert torch.equal(clone.prob, src.prob)
+    assert clone.engine_plan() == src.engine_plan() == plan, "three certain slots: nobody had to grow"
 
 
 def test_a_stage_context_returns_every_buffer(nets):

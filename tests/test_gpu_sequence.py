@@ -793,11 +793,22 @@ def test_engine_options_are_explicit_per_engine_and_inherited_by_clones(nets, mo
     assert all(iou(x, y) >= 1 - 1e-3 for x, y in zip(ra, rb))          # another batching = another M of the same GEMMs: fp32 rounding only
     monkeypatch.setenv("STCN_LOOKAHEAD", "0")
     monkeypatch.setenv("STCN_DECODE_BATCH", "1")
+    monkeypatch.setenv("STCN_DUAL_SWEEP", "0")
     c = copy.deepcopy(a)
     assert c.engine_options() == a.engine_options()
+    plan = a.engine_plan()
+    assert c.engine_plan() == plan and plan["dual_sweep"] == 1 and plan["bank_lo"] == 4      # the whole plan, the bank's capacity included
     assert np.array_equal(c.interact(msk[:, 4], 4), a.interact(msk[:, 4], 4))
     with pytest.raises(TypeError, match="unknown engine_options"):
         InferenceCore(nets[0], nets[1], img, 1, engine_options={"look_ahead": 0})
+    # mirrored: a serial source stays serial in a clone made under the default environment
+    monkeypatch.setenv("STCN_LOOKAHEAD", "2")
+    s = InferenceCore(nets[0], nets[1], img, 1, mem_freq=3)
+    assert s.engine_plan()["dual_sweep"] == 0 and s.engine_plan()["bank_lo"] == 0
+    for name in ("STCN_LOOKAHEAD", "STCN_DECODE_BATCH", "STCN_DUAL_SWEEP"):
+        monkeypatch.delenv(name)
+    sc = copy.deepcopy(s)
+    assert sc.engine_plan() == s.engine_plan() and sc.engine_plan()["dual_sweep"] == 0 and sc.engine_plan()["bank_lo"] == 0
 
 
 def test_a_clone_keeps_the_launch_knobs_of_its_source(nets, monkeypatch):

@@ -1,6 +1,6 @@
 // stage_host_check.cpp - the host side of the stage API (stages.cpp) that runs before any device call, as a stand-alone program for a
 // sanitizer build on a machine WITHOUT a GPU: argument validation of every stcn_stage_* / stcn_aggregate_wbg / stcn_fusion_model_create
-// export and the growth rule of the bank staging.  Build and run:  make -C eva_vos_amd/csrc stage-host-check
+// export, the growth rule of the bank staging and the engine plan (plan_engine, bank_slots_needed) at its extremes.  Build and run:  make -C eva_vos_amd/csrc stage-host-check
 // (host code with -fsanitize=address,undefined; the program links the library's objects, nothing is loaded into another process).
 #include <cstdio>
 #include <cstring>
@@ -83,6 +83,33 @@ int main() {
         EXPECT(q.take_fitting(1, &got, &cap) && got.release() == &mem[3] && cap == 100);
         EXPECT(!q.take_fitting(301, &got, &cap) && q.take_fitting(300, &got, &cap) && got.release() == &mem[0] && q.bufs.empty());
         EXPECT(!q.take_fitting(0, &got, &cap));
+    }
+    {   // the engine plan at its extremes: one frame, one frame more than the key cache, the most objects, a bank insertion at every frame
+        // and none at all.  Whatever is asked for, every workspace is built for >= 1 frame and the bank holds a whole-clip sweep
+        const stcn::EngineEnv env;                     // the defaults: this program reads no environment
+        const stcn_engine_opts none{-1, -1, -1, -1}, wild{1 << 30, 1 << 30, 1 << 30, 1 << 30}, zero{0, 0, 0, 0};
+        const int shapes[][3] = {{1, 1, 1}, {1, 1, 5}, {2, STCN_MAX_OBJECTS, 1}, {3, 1, 1000}, {106, 1, 1}, {107, 1, 1}, {107, STCN_MAX_OBJECTS, 200}, {9, STCN_MAX_OBJECTS, 5}};
+        for (const auto &s : shapes)
+            for (const stcn_engine_opts &o : {none, wild, zero})
+                for (int fuse = 0; fuse < 2; ++fuse) {
+                    const int T = s[0], k = s[1], mf = s[2];
+                    const stcn::EnginePlan p = stcn::plan_engine(T, k, mf, fuse != 0, o, env);
+                    EXPECT(p.n_slots == (T < 106 ? T : 106) && p.mem_freq == mf);
+                    EXPECT(p.group >= 1 && p.group <= stcn::MAX_DECODE_GROUP && p.group <= (mf > 1 ? mf : 1) && (p.group == 1 || p.group * k <= 16));
+                    EXPECT(p.key_batch >= 1 && p.key_batch <= 8);
+                    EXPECT(p.main.key_batch >= 1 && p.main.group == p.group && p.side.key_batch >= 1 && p.side.group == 1);
+                    EXPECT(!p.dual_sweep || (T >= 3 && T <= p.n_slots && p.lookahead > 0));
+                    EXPECT(!p.fuse_side || (fuse && p.has_side));
+                    EXPECT(p.bank_lo == (p.dual_sweep ? (T - 1) / mf + 2 : 0));
+                    EXPECT(p.bank_initial == stcn::bank_slots_needed(p, T - 1, 8) && p.bank_initial == p.bank_lo + (T - 1) / mf + 1 + 8);
+                    // an interaction next to an interacted frame (span 0) still has room for its certain slot; longer spans never need less
+                    EXPECT(stcn::bank_slots_needed(p, 0, 1) == p.bank_lo + 2);
+                    EXPECT(stcn::bank_slots_needed(p, T - 1, 60) >= stcn::bank_slots_needed(p, T / 2, 60));
+                }
+        const stcn::EnginePlan a = stcn::plan_engine(107, 1, 1, true, none, env);      // a clip that recycles its cache keeps fuse_side, nothing else
+        EXPECT(a.lookahead == 0 && a.lookahead_req == 2 && a.fuse_side && a.has_side && !a.dual_sweep && a.side.key_batch == 1 && a.bank_initial == 115);
+        const stcn::EnginePlan b = stcn::plan_engine(106, 1, 1, true, none, env);
+        EXPECT(b.lookahead == 2 && b.dual_sweep && b.bank_lo == 107 && b.bank_initial == 107 + 106 + 8);
     }
     std::printf(failures ? "stage_host_check: %d FAILED\n" : "stage_host_check: all checks passed\n", failures);
     return failures ? 1 : 0;
